@@ -10,13 +10,25 @@ verdict buffer already resident in HBM.
 N > 1: one process per GPU (torchrun; `--gpus N` without torchrun starts the same ranks as children),
 every rank runs its own 16M-packet shard (weak scaling) and the timed steps form one shard epoch whose
 map deltas are all-reduced over RCCL (or replayed in order) inside the timed region — the same code
-path for N = 1..8. After the timed region every rank checks its verdicts and its map against truth
-derived from the generated headers (`verified`). The default line also carries BASELINE configs[4]
-as the `c5` side line (33.5M packets per GPU, per-flow HASH counters, the per-flow delta exchange
-timed separately, verified the same way). Prints ONE JSON line (rank 0) with roofline and
-cpu_baseline objects.
+path for N = 1..8. Prints ONE JSON line (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--packets P]
+A plain run does only what the headline figure needs: it sets up, warms up, times the `--steps` steps,
+writes the outputs if `--dump-outputs` is given, and prints the line (its roofline object comes from the
+timed steps' own HIP-event kernel times). Everything else is behind `--full`: after the timed region
+every rank checks its verdicts and its map against truth derived from the generated headers
+(`verified`); the line also carries BASELINE configs[4] as the `c5` side line (33.5M packets per GPU,
+per-flow HASH counters, the per-flow delta exchange timed separately, verified the same way), the `c3`
+and `c4` side lines, the ordered-path and keyed streams, the host-memory `e2e` rate and the
+`cpu_baseline` object. The `--no-*` options drop single parts of a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (rank 0):
+`verdicts.npy` (float32; batches above 4,194,304 packets: the packets at a fixed, seeded sample of
+that many indices, in index order) and, for a workload with maps, `map<m>_values.npy` (float64: map m's
+values as 64-bit words in xe_map_dump order, after the warm-up and timed steps). The inputs are
+generated from the packet index alone, so two runs with the same arguments dump comparable arrays.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--packets P] [--full]
+                  [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -418,6 +430,45 @@ def verify(name: str, vm, start: int, n: int, runs: int, d_ver, dist, world: int
                     f"{world} shard(s) of the header-derived per-run effect", "check_s": round(time.perf_counter() - t0, 2)}
 
 
+DUMP_SAMPLE = 4 * 1024 * 1024  # rows of one dumped array (verdicts.npy: 16 MB; the whole dump stays under 64 MB)
+DUMP_SEED = 0x58444531
+
+
+def _dump_rows(a: np.ndarray, limit: int = DUMP_SAMPLE) -> np.ndarray:
+    """`a`, or its rows at a fixed, seeded sample of `limit` indices (in index order) when it has more."""
+    if len(a) <= limit:
+        return a
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), size=limit, replace=False))
+    return a[idx]
+
+
+def dump_outputs(out_dir: str, vm, d_ver) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy — the verdict
+    buffer (verdicts.npy, float32) and the state of every ARRAY / HASH map after the warm-up and timed
+    steps (map<m>_values.npy, float64: the values as 64-bit words, HASH entries in xe_map_dump's key
+    order). Arrays above DUMP_SAMPLE rows are sampled (_dump_rows). Returns {file name: shape}."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"verdicts": _dump_rows(d_ver.cpu().numpy().view(np.uint32)).astype(np.float32)}
+    budget = 64_000_000 - arrays["verdicts"].nbytes
+    for m in sorted(vm.map_defs):
+        got = vm.map_dump(m)
+        if isinstance(got, list):  # QUEUE / STACK / PERF records: no bench workload has one
+            continue
+        raw = np.frombuffer(got, np.uint8) if isinstance(got, bytes) else np.ascontiguousarray(got[1]).reshape(-1)
+        vs = vm.map_defs[m].value_size
+        if vs % 8 or raw.size == 0:
+            continue
+        a = _dump_rows(raw.view(np.uint64).reshape(-1, vs // 8), DUMP_SAMPLE // (vs // 8)).astype(np.float64)
+        if a.nbytes > budget:
+            continue
+        budget -= a.nbytes
+        arrays[f"map{m}_values"] = a
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", a)
+    return {f"{k}.npy": list(a.shape) for k, a in arrays.items()}
+
+
 def _dsync(dev) -> None:
     """torch.cuda.synchronize on a GPU device; nothing on the CPU (the gloo tests drive run_epochs with
     host-simulation VMs over CPU tensors)."""
@@ -597,7 +648,15 @@ def main() -> None:
     ap.add_argument("--sync", action="store_true", help="one synchronous xe_run_batch_device per step (no pipelining)")
     ap.add_argument("--keyed-packets", type=int, default=4 * 1024 * 1024,
                     help="C3-learn batch of the keyed ordered-execution line (C2 runs only)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the self-check, the e2e rate, the c3 / c4 / c5 side lines, the "
+                         "ordered-path and keyed streams and the CPU baseline (each with its own --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's verdicts and the map state as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, (dump,) print
+        args.no_verify = args.no_e2e = args.no_c3 = args.no_c5 = args.no_c4 = args.no_ordered = True
+        args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
@@ -654,7 +713,8 @@ def main() -> None:
         steps_retired += st["steps"]
         status_ok += st["status_count"][0]
         grid = st["grid_blocks"]
-    # self-check outside the timed region, before anything else runs on this VM
+    # the timed path's outputs, then the self-check: outside the timed region, before anything else runs on this VM
+    dumped = dump_outputs(args.dump_outputs, vm, d_ver) if args.dump_outputs and rank == 0 else None
     check = None if args.no_verify else verify(name, vm, start, n, args.warmup + args.steps, d_ver, dist, world, dev)
 
     total_pkts = n * world * args.steps
@@ -720,6 +780,8 @@ def main() -> None:
                        "batches": "pipelined (xe_run_batch_device_async, depth 3, device-side conflict check)"
                                   if not args.sync else "synchronous (xe_run_batch_device)",
                        "grid": grid},
+            "full": args.full,
+            "dumped_outputs": dumped,
             "verified": None if check is None else check["verified"],
             "verification": check,
             "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",

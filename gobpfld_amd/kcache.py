@@ -80,8 +80,7 @@ def fill(sources, cache_dir: str | os.PathLike, arch: str = "gfx950", workers: i
          lib_path: str | os.PathLike | None = None) -> list[str]:
     """Compile every distinct source into `cache_dir` with a pool of worker processes; returns the
     error texts of the sources that failed (their VMs fall back as their own build would)."""
-    from concurrent.futures import ProcessPoolExecutor
-    import multiprocessing as mp
+    import sys
     from . import _native as N
     uniq = list(dict.fromkeys(sources))
     if not uniq:
@@ -90,6 +89,25 @@ def fill(sources, cache_dir: str | os.PathLike, arch: str = "gfx950", workers: i
     os.makedirs(d, exist_ok=True)
     path = os.fspath(lib_path or N.product_path())
     n = min(workers or default_workers(), len(uniq))
+    # A spawned worker runs the parent's __main__ file again before it takes a job. A parent whose program
+    # came from standard input (`python - <<EOF`) has __main__.__file__ == "<stdin>", which no worker can
+    # open: the pool would break before its first compile. Such a __main__ is hidden while the pool lives
+    # (the workers need nothing from it: _worker_init / _worker_compile are this module's).
+    main = sys.modules.get("__main__")
+    main_file = getattr(main, "__file__", None)
+    hide = main_file is not None and getattr(main, "__spec__", None) is None and not os.path.exists(main_file)
+    if hide:
+        del main.__file__
+    try:
+        return _fill(uniq, arch, d, path, n)
+    finally:
+        if hide:
+            main.__file__ = main_file
+
+
+def _fill(uniq: list[str], arch: str, d: str, path: str, n: int) -> list[str]:
+    from concurrent.futures import ProcessPoolExecutor
+    import multiprocessing as mp
     with ProcessPoolExecutor(max_workers=n, mp_context=mp.get_context("spawn"), initializer=_worker_init,
                              initargs=(path,)) as ex:
         res = list(ex.map(_worker_compile, [(s, arch, d) for s in uniq]))

@@ -55,3 +55,24 @@ def test_host_generated_sources_equal_device_sources(gpu_lib, hostsim_lib, name)
     case = _case(name)
     assert aot.sources([case], lib=hostsim_lib) == aot.sources([case], lib=gpu_lib)
     assert len(aot.sources([case], lib=hostsim_lib, variants=(2,))) == 1  # the verdict-only variant
+
+
+def test_fill_from_a_program_on_standard_input(built, tmp_path):
+    """kcache.fill's workers are spawned processes, which run the parent's __main__ file again; a parent
+    whose program came from standard input has none they could open. The pool must still compile."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    prog = (f"import sys; sys.path[:0] = [{str(root)!r}, {str(root / 'tests')!r}]\n"
+            "from gobpfld_amd import aot, kcache\n"
+            "from gobpfld_amd.emulator import Settings\n"
+            "from parity import config_case\n"
+            "prog, maps, entries, _, _ = config_case('c1', 16, 4096)\n"
+            "srcs = aot.sources([(prog, maps, entries, Settings())], variants=(0,))\n"
+            f"errs = kcache.fill(srcs, {str(tmp_path)!r}, workers=1)\n"
+            "assert len(srcs) == 1 and not errs, errs\n"
+            "assert sys.modules['__main__'].__file__ == '<stdin>'\n")
+    r = subprocess.run([sys.executable, "-"], input=prog, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert len(list(tmp_path.glob("xe_*.co"))) == 1

@@ -70,3 +70,31 @@ def test_device_batch_layout_matches_host_batch():
         assert np.array_equal(d_umem.numpy(), umem), name
         assert np.array_equal(descs, descs2), name
         assert np.array_equal(d_desc.numpy(), descs2.view(np.uint8)), name
+
+
+def test_dump_outputs_are_float_arrays_and_repeat(hostsim_lib, tmp_path):
+    """bench.py --dump-outputs: the verdicts (float32) and every map's values (float64 words) of a run,
+    sampled at a fixed set of rows above the limit; the same state dumps the same files."""
+    import torch
+    B = _bench()
+    n = 5000
+    for name, maps in (("c2", 1), ("c3", 1), ("c4", 0)):
+        vm = VM(Settings(), lib=hostsim_lib)
+        W.setup_vm(vm, name)
+        umem, descs = W.build_batch(name, 0, n)
+        r = vm.run_batch(umem, descs)
+        d_ver = torch.from_numpy(r.verdicts.astype(np.int32))
+        a, b = (B.dump_outputs(str(tmp_path / name / k), vm, d_ver) for k in "ab")
+        assert a == b and sorted(a) == sorted(["verdicts.npy"] + [f"map{m + 1}_values.npy" for m in range(maps)])
+        for f in a:
+            x, y = (np.load(tmp_path / name / k / f) for k in "ab")
+            assert x.dtype == (np.float32 if f == "verdicts.npy" else np.float64) and np.array_equal(x, y)
+        assert np.array_equal(np.load(tmp_path / name / "a" / "verdicts.npy"), r.verdicts.astype(np.float32))
+        if name == "c2":
+            want = np.frombuffer(vm.map_dump(1), np.uint64).astype(np.float64).reshape(-1, 1)
+            assert np.array_equal(np.load(tmp_path / name / "a" / "map1_values.npy"), want)
+        vm.close()
+    big = np.arange(10_000, dtype=np.uint32)
+    s = B._dump_rows(big, 1000)
+    assert len(s) == 1000 and (np.diff(s) > 0).all() and np.array_equal(s, B._dump_rows(big, 1000))
+    assert B._dump_rows(big, 10_000) is big
