@@ -59,6 +59,10 @@ class PcapInfo(C.Structure):  # include/xdpemu_io.h
                 ("swapped", C.c_uint32), ("first_record", C.c_uint64)]
 
 
+class DispatchCounts(C.Structure):  # xe_dispatch_counts (include/xdpemu_io.h)
+    _fields_ = [("offset", C.c_uint32 * 6), ("invalid", C.c_uint32), ("failed", C.c_uint32)]
+
+
 class TraceRec(C.Structure):  # xe_trace_rec: one Step's VM.String (emulator/vm.go:248-270)
     _fields_ = [("packet", C.c_uint32), ("step", C.c_uint32), ("pc", C.c_int32), ("pi", C.c_int32),
                 ("sf", C.c_uint32), ("kind", C.c_uint8 * 11), ("pad", C.c_uint8), ("val", C.c_int64 * 11)]
@@ -156,6 +160,9 @@ _SIGS = {
                             C.c_uint64, C.c_uint32, P, P, P, C.POINTER(C.c_uint32)]),
     "pcap_pack": (C.c_int, [P, C.c_uint64, P, C.POINTER(C.c_uint64), P, C.c_uint64, C.c_uint32, C.c_uint32,
                             C.c_uint32, P, P, P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dispatch_scratch_bytes": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
+    "dispatch_device": (C.c_int, [P, P, P, C.c_uint32, P, P, P, P, C.c_uint64, P]),
+    "gather_device": (C.c_int, [P, C.c_uint64, P, P, C.c_uint32, C.c_uint32, P, C.c_uint32, P, C.c_uint64, P, P, P]),
 }
 
 # every symbol include/xdpemu.h declares (checked by tests/test_abi.py)
@@ -172,7 +179,11 @@ HEADER_SYMBOLS = [
     "xe_kernel_cache_stats",
     "xe_cancel", "xe_trace_config", "xe_trace_read", "xe_set_helper", "xe_reset_helper",
 ]
-IO_HEADER_SYMBOLS = ["xe_pcap_header", "xe_pcap_count", "xe_pcap_fill", "xe_pcap_pack"]  # include/xdpemu_io.h
+IO_HEADER_SYMBOLS = ["xe_pcap_header", "xe_pcap_count", "xe_pcap_fill", "xe_pcap_pack",  # include/xdpemu_io.h
+                     "xe_dispatch_scratch_bytes", "xe_dispatch_device", "xe_gather_device"]
+# the output side of include/xdpemu_io.h
+ACT_ABORTED, ACT_DROP, ACT_PASS, ACT_TX, ACT_REDIRECT, ACT_COUNT = 0, 1, 2, 3, 4, 5
+XE_DISPATCH_TILE = 2048
 
 
 class Lib:

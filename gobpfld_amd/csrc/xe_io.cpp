@@ -1,5 +1,5 @@
 // Capture files -> AF_XDP-shaped UMEM frames + rx descriptors (include/xdpemu_io.h).
-// Host-only; the layout it produces is the reference's XSK one (xsk.go:695-757): frame starts are
+// The ingestion half is host-only; the layout it produces is the reference's XSK one (xsk.go:695-757): frame starts are
 // multiples of FrameSize, the descriptor points at frame start + headroom (the kernel's rx address,
 // which addrToFrameStart, xsk.go:504-506, rounds back down when the frame is recycled).
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/xdpemu_io.h"
+#include "xe_dispatch.h"
 
 namespace {
 
@@ -154,4 +155,98 @@ extern "C" int xe_pcap_pack(const uint8_t* f, uint64_t len, const xe_pcap_info* 
   *filled = k;
   *used = at < buf_len ? at : buf_len;
   return XE_OK;
+}
+
+// ---------------------------------------------------------------- output side: verdict dispatch
+// The product hands the work to the kernels of xe_dispatch.hip; the host simulation states the same
+// contract as loops over host pointers.
+namespace {
+inline bool misaligned(const void* p, uintptr_t a) { return (uintptr_t(p) & (a - 1)) != 0; }
+}  // namespace
+
+extern "C" int xe_dispatch_scratch_bytes(uint32_t n, uint64_t* bytes) {
+  if (!bytes) return XE_ERR_INVAL;
+  *bytes = xe_dsp_scratch(n);
+  return XE_OK;
+}
+
+extern "C" int xe_dispatch_device(const void* d_desc, const void* d_verdicts, const void* d_results, uint32_t n,
+                                  void* d_out_desc, void* d_out_index, void* d_counts, void* d_scratch, uint64_t scratch_bytes,
+                                  void* stream) {
+  if (!d_counts || misaligned(d_counts, 4)) return XE_ERR_INVAL;
+  if (n) {
+    if (!d_desc || !d_verdicts || !d_out_desc || !d_scratch || scratch_bytes < xe_dsp_scratch(n)) return XE_ERR_INVAL;
+    if (misaligned(d_desc, 16) || misaligned(d_out_desc, 16) || misaligned(d_verdicts, 4) || misaligned(d_out_index, 4) ||
+        misaligned(d_scratch, 16))
+      return XE_ERR_INVAL;
+    const uintptr_t in = uintptr_t(d_desc), out = uintptr_t(d_out_desc), span = uintptr_t(n) * sizeof(xe_desc);
+    if (in < out + span && out < in + span) return XE_ERR_INVAL;
+  }
+#ifndef XE_HOSTSIM
+  return xe_launch_dispatch(d_desc, d_verdicts, d_results, n, d_out_desc, d_out_index, d_counts, d_scratch, stream) ? XE_ERR_DEVICE
+                                                                                                                     : XE_OK;
+#else
+  (void)stream;
+  const xe_desc* desc = static_cast<const xe_desc*>(d_desc);
+  const uint32_t* ver = static_cast<const uint32_t*>(d_verdicts);
+  const xe_result* res = static_cast<const xe_result*>(d_results);
+  xe_desc* out = static_cast<xe_desc*>(d_out_desc);
+  uint32_t* index = static_cast<uint32_t*>(d_out_index);
+  xe_dispatch_counts c{};
+  uint32_t rows[kDspRows] = {};
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t r = xe_dsp_row(ver[i], res ? res[i].status : XE_ST_OK);
+    rows[r]++;
+    if (r > 4) rows[0]++;
+  }
+  for (uint32_t k = 0; k < XE_ACT_COUNT; k++) c.offset[k + 1] = c.offset[k] + rows[k];
+  c.invalid = rows[kDspInvalid];
+  c.failed = rows[kDspFailed];
+  uint32_t at[XE_ACT_COUNT];
+  memcpy(at, c.offset, sizeof(at));
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t pos = at[xe_dsp_class(xe_dsp_row(ver[i], res ? res[i].status : XE_ST_OK))]++;
+    out[pos] = desc[i];
+    if (index) index[pos] = i;
+  }
+  memcpy(d_counts, &c, sizeof(c));
+  return XE_OK;
+#endif
+}
+
+extern "C" int xe_gather_device(const void* d_src, uint64_t src_len, const void* d_sorted_desc, const void* d_counts, uint32_t cls,
+                                uint32_t max_count, const void* d_frames, uint32_t frame_room, void* d_dst, uint64_t dst_len,
+                                void* d_out_desc, void* d_rejected, void* stream) {
+  if (!d_counts || !d_rejected || cls >= XE_ACT_COUNT || misaligned(d_counts, 4) || misaligned(d_rejected, 4)) return XE_ERR_INVAL;
+  if (max_count && (!d_src || !d_sorted_desc || !d_frames || !d_dst || !d_out_desc)) return XE_ERR_INVAL;
+  if (misaligned(d_sorted_desc, 16) || misaligned(d_out_desc, 16) || misaligned(d_frames, 8)) return XE_ERR_INVAL;
+#ifndef XE_HOSTSIM
+  return xe_launch_gather(d_src, src_len, d_sorted_desc, d_counts, cls, max_count, d_frames, frame_room, d_dst, dst_len,
+                          d_out_desc, d_rejected, stream)
+             ? XE_ERR_DEVICE
+             : XE_OK;
+#else
+  (void)stream;
+  const uint8_t* src = static_cast<const uint8_t*>(d_src);
+  const xe_desc* sorted = static_cast<const xe_desc*>(d_sorted_desc);
+  const uint64_t* frames = static_cast<const uint64_t*>(d_frames);
+  uint8_t* dst = static_cast<uint8_t*>(d_dst);
+  xe_desc* out = static_cast<xe_desc*>(d_out_desc);
+  xe_dispatch_counts c;
+  memcpy(&c, d_counts, sizeof(c));
+  uint32_t rejected = 0;
+  const uint32_t lo = c.offset[cls], hi = c.offset[cls + 1];
+  if (lo <= hi && hi <= c.offset[XE_ACT_COUNT]) {
+    const uint32_t cnt = std::min(hi - lo, max_count);
+    for (uint32_t k = 0; k < cnt; k++) {
+      const xe_desc d = sorted[lo + k];
+      const bool ok = xe_gather_ok(d.addr, d.len, src_len, frame_room, frames[k], dst_len);
+      if (ok) memcpy(dst + frames[k], src + d.addr, d.len);
+      out[k] = xe_desc{frames[k], ok ? d.len : 0, 0};
+      rejected += !ok;
+    }
+  }
+  memcpy(d_rejected, &rejected, 4);
+  return XE_OK;
+#endif
 }

@@ -293,6 +293,7 @@ class PcapRun:
     verdict_count: dict = field(default_factory=dict)  # R0 value -> packets (status OK)
     status_count: list = field(default_factory=lambda: [0] * 8)
     verdicts: np.ndarray | None = None
+    action_count: list | None = None  # dispatch=True: packets per XDP action 0..4 (xe_dispatch_counts)
 
     @property
     def mpps(self) -> float:
@@ -300,10 +301,15 @@ class PcapRun:
 
 
 def run_pcap(vm, pcap: PcapFile, batch: int = 1 << 20, staging_bytes: int | None = None, align: int = 64,
-             keep_verdicts: bool = False) -> PcapRun:
+             keep_verdicts: bool = False, dispatch: bool = False) -> PcapRun:
     """Stream a capture through the device emulator: native packing into two pinned staging
     buffers, H2D on a side stream overlapped with the previous batch's kernel, verdicts back.
-    `vm` is a gobpfld_amd.emulator.VM on the product library."""
+    `vm` is a gobpfld_amd.emulator.VM on the product library.
+
+    dispatch=True partitions each batch by action on the compute stream (gobpfld_amd.dispatch) and
+    accumulates `action_count` from the 32-byte counts record: a packet whose run failed, or whose
+    verdict is no XDP action, counts as aborted. The verdicts then come back only with keep_verdicts
+    (`verdict_count` is filled from them, so it stays empty without)."""
     import torch
 
     d_desc_t = N.np_dtypes()[0]
@@ -315,6 +321,12 @@ def run_pcap(vm, pcap: PcapFile, batch: int = 1 << 20, staging_bytes: int | None
     d_ver = [torch.empty(batch, dtype=torch.int32, device="cuda") for _ in range(2)]
     h2d, comp = torch.cuda.Stream(), torch.cuda.Stream()
     out = PcapRun()
+    if dispatch:
+        from .dispatch import Dispatcher
+        dsp = Dispatcher(vm.lib)
+        d_res = [torch.empty(batch * 16, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        part = [None, None]
+        out.action_count = [0] * N.ACT_COUNT
     kept = []
 
     def parse(i):
@@ -329,13 +341,27 @@ def run_pcap(vm, pcap: PcapFile, batch: int = 1 << 20, staging_bytes: int | None
             ev.record(h2d)
         return ev
 
+    def run_dispatch(i, n, used, ev):
+        comp.wait_event(ev)
+        st = vm.run_batch_device(d_buf[i].data_ptr(), max(used, 1), d_desc[i].data_ptr(), n, d_results=d_res[i].data_ptr(),
+                                 d_verdicts=d_ver[i].data_ptr(), stream=comp.cuda_stream)
+        part[i] = dsp.run(d_desc[i].data_ptr(), d_ver[i].data_ptr(), n, d_results=d_res[i].data_ptr(), want_index=False,
+                          stream=comp.cuda_stream, into=part[i])
+        v = None
+        if keep_verdicts:
+            with torch.cuda.stream(comp):
+                v = d_ver[i][:n].cpu()
+        return st, v, part[i].counts().sizes
+
     def run(i, n, used, ev):
+        if dispatch:
+            return run_dispatch(i, n, used, ev)
         comp.wait_event(ev)
         st = vm.run_batch_device(d_buf[i].data_ptr(), max(used, 1), d_desc[i].data_ptr(), n,
                                  d_verdicts=d_ver[i].data_ptr(), stream=comp.cuda_stream)
         with torch.cuda.stream(comp):
             v = d_ver[i][:n].cpu()
-        return st, v
+        return st, v, None
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -351,14 +377,17 @@ def run_pcap(vm, pcap: PcapFile, batch: int = 1 << 20, staging_bytes: int | None
             n2, used2 = nxt.result()
             # the other staging/device pair is free: its batch (k - 1) finished before run(k) began
             ev2 = upload((k + 1) % 2, n2, used2) if n2 else None
-            st, v = fut.result()
+            st, v, sizes = fut.result()
             out.packets += n
             out.batches += 1
             out.device_ms += st["kernel_ms"]
             out.status_count = [a + b for a, b in zip(out.status_count, st["status_count"])]
-            vals, cnt = np.unique(v.numpy().view(np.uint32), return_counts=True)
-            for a, b in zip(vals.tolist(), cnt.tolist()):
-                out.verdict_count[a] = out.verdict_count.get(a, 0) + b
+            if sizes is not None:
+                out.action_count = [a + b for a, b in zip(out.action_count, sizes)]
+            if v is not None:
+                vals, cnt = np.unique(v.numpy().view(np.uint32), return_counts=True)
+                for a, b in zip(vals.tolist(), cnt.tolist()):
+                    out.verdict_count[a] = out.verdict_count.get(a, 0) + b
             if keep_verdicts:
                 kept.append(v.numpy().view(np.uint32).copy())
             n, used, ev = n2, used2, ev2
