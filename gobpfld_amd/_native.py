@@ -146,6 +146,13 @@ _SIGS = {
     "map_state_bytes": (C.c_int, [P, C.c_int32, C.POINTER(C.c_uint64)]),
     "map_state_export": (C.c_int, [P, C.c_int32, P, P]),
     "map_state_import": (C.c_int, [P, C.c_int32, P, P]),
+    "map_lookup_batch_device": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P, P]),
+    "map_update_batch_device": (C.c_int, [P, C.c_int32, P, P, C.c_uint64, P]),
+    "map_delete_batch_device": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P]),
+    "map_lookup_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P]),
+    "map_update_batch_staged": (C.c_int, [P, C.c_int32, P, P, C.c_uint64]),
+    "map_delete_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P]),
+    "debug_map_traffic": (C.c_int, [P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "multi_create": (C.c_int, [P, C.c_uint32, C.POINTER(P)]),
     "multi_destroy": (None, [P]),
     "multi_last_error": (C.c_char_p, [P]),
@@ -175,6 +182,8 @@ HEADER_SYMBOLS = [
     "xe_map_state_import",
     "xe_multi_create", "xe_multi_destroy", "xe_run_batch_multi", "xe_multi_last_error", "xe_debug_set_schedule",
     "xe_debug_set_lru_epoch", "xe_debug_map_pool",
+    "xe_map_lookup_batch_device", "xe_map_update_batch_device", "xe_map_delete_batch_device",
+    "xe_map_lookup_batch", "xe_map_update_batch_staged", "xe_map_delete_batch", "xe_debug_map_traffic",
     "xe_set_kernel_cache", "xe_kernel_source", "xe_compile_kernel_source", "xe_kernel_object_name",
     "xe_kernel_cache_stats",
     "xe_cancel", "xe_trace_config", "xe_trace_read", "xe_set_helper", "xe_reset_helper",

@@ -1,0 +1,369 @@
+// Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
+// xe_map_update_batch_device, xe_map_delete_batch_device): the per-key decision logic that the kernels
+// (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
+// declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
+//
+// A batch is a sequence of steps, one launch each (a step's writes are the next step's reads: the
+// phases are kernel boundaries, no workgroup waits on another):
+//
+//   lookup   FIND    one key per lane: probe (read-only), found[i], slot[i]; values of up to
+//                    kMoInline bytes are written by the same lane
+//            VALUE   larger values: a sub-group of lanes copies value i (or zero-fills it)
+//   update   LOCATE  one key per lane: the key's record, or a record claimed for it. A claim is one CAS
+//                    on the record's word 0 that also names the claiming batch entry (BUSY | (i+1) << 32),
+//                    so a repetition of the key that meets the claim compares its key with batch entry
+//                    i's — input bytes, complete before the launch — and never waits for the claimer.
+//                    The claims are counted: the distinct absent keys of the batch.
+//            UNDO    (the batch does not fit, or an ARRAY index is out of range) every claim is put back:
+//                    the table is bit for bit what it was
+//            MARK    the claimer writes the key words; every entry raises the record's "last writer"
+//                    word to its batch index + 1 (atomic max): the last repetition wins, decided here,
+//                    before any value byte moves
+//            COPY    a sub-group per entry; the winner copies its value into the map and into the delta
+//                    base, then publishes the record as FULL (clearing VLEN0 and the last-writer word)
+//   delete   FIND    as the lookup's (found[i] is "present before the call" for every repetition)
+//            CLAIM   one CAS FULL -> TOMB | (i+1) << 32 per present key: one entry per distinct key wins
+//            ZERO    the winner's sub-group zeroes the value (map and delta base), the record becomes a
+//                    plain tombstone and the count drops
+//
+// The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
+// an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
+// index in a buffer of the map's own that is zero between calls. Both are zero again when a call returns.
+//
+// A deleted record keeps its key words. A tombstone holding key words is what the keyed path calls a
+// reservation for that key (xe_interp.h hash_reserve / hash_claim): a later insert of the same key, by a
+// keyed batch or by LOCATE, takes that record again, so a flow that is expired and learned again and again
+// keeps using one record instead of a fresh one each time; its value bytes are zero, as a reservation's are.
+// Clearing the words would turn every deleted record into a reservation for the all-zero key instead.
+// Tombstones of keys that never come back stay until the map next visits the host (drop_tombstones); when
+// they have used up a probe chain's free records LOCATE says so (kMoErrFull) and the runtime compacts the
+// table through the host once.
+#ifndef XE_MAPOPS_H
+#define XE_MAPOPS_H
+
+#include "xe_internal.h"
+
+enum : uint32_t {
+  XE_MO_LOOKUP_FIND = 0, XE_MO_LOOKUP_VALUE,
+  XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY,
+  XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO,
+  XE_MO_STEPS
+};
+
+constexpr uint32_t kMoInline = 16;           // values up to this many bytes move on their key's lane
+constexpr uint32_t kMoFresh = 0x80000000u;   // slot[i]: this entry claimed the record (update)
+constexpr uint32_t kMoVlen0 = 0x40000000u;   // slot[i]: the record's value reads as zeros (lookup)
+constexpr uint32_t kMoSlotMask = 0x3fffffffu;  // (cap <= 2^27, ARRAY indices are checked against it)
+constexpr uint32_t kMoAbsent = kMoSlotMask;
+// counters of a batch (u32 words of the scratch)
+constexpr uint32_t kMoNew = 0, kMoErr = 1, kMoGone = 2, kMoCounters = 16;
+constexpr uint32_t kMoErrRange = 1, kMoErrFull = 2;  // an ARRAY index out of range; no free record in the table
+
+struct XeMapOp {
+  uint32_t kind;  // XE_DM_ARRAY / XE_DM_HASH
+  uint32_t key_size, value_size, max_entries, cap, kwords, rwords;
+  uint32_t n;             // batch entries
+  uint64_t* recs;         // HASH: slot records
+  uint8_t* vals;
+  uint8_t* snap;          // the delta base (HostMap::d_snap): kept equal to vals on the slots a call writes
+  uint32_t* count;        // HASH: entry count
+  uint32_t* win;          // ARRAY: last-writer word per index
+  const uint8_t* keys;    // n x key_size (ARRAY: n x 4)
+  const uint8_t* values_in;
+  uint8_t* values_out;
+  uint8_t* found;         // may be null
+  uint32_t* slot;         // [n] scratch
+  uint32_t* ctr;          // [kMoCounters] scratch, zero at the batch's start
+};
+
+// lanes that share one value (a power of two <= 64)
+inline uint32_t xe_mo_lanes(uint32_t value_size) {
+  return value_size <= kMoInline ? 1u : value_size <= 64 ? 4u : value_size <= 1024 ? 16u : 64u;
+}
+
+// ---------------------------------------------------------------- atomics (plain on the host: one thread)
+XE_HD uint64_t mo_load64(uint64_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __hip_atomic_load((unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  return *p;
+#endif
+}
+XE_HD uint64_t mo_cas64(uint64_t* p, uint64_t expect, uint64_t v) {  // the value found
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned long long c = expect;
+  __hip_atomic_compare_exchange_strong((unsigned long long*)p, &c, (unsigned long long)v, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  return c;
+#else
+  const uint64_t c = *p;
+  if (c == expect) *p = v;
+  return c;
+#endif
+}
+XE_HD void mo_max32(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  if (*p < v) *p = v;
+#endif
+}
+XE_HD void mo_add32(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *p += v;
+#endif
+}
+XE_HD void mo_or32(uint32_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *p |= v;
+#endif
+}
+
+// ---------------------------------------------------------------- keys
+// Batch entry i's key as zero-padded words (HASH), as HostMap::pack_key makes them.
+XE_HD void mo_load_key(const XeMapOp& o, uint32_t i, uint64_t* kw) {
+  const uint8_t* k = o.keys + uint64_t(i) * o.key_size;
+  if (!(o.key_size & 7) && !(uintptr_t(o.keys) & 7)) {
+    for (uint32_t w = 0; w < XE_MAX_KEY / 8; w++) kw[w] = w < o.kwords ? ((const uint64_t*)k)[w] : 0;
+    return;
+  }
+  for (uint32_t w = 0; w < XE_MAX_KEY / 8; w++) {
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < 8; b++)
+      if (w * 8 + b < o.key_size) v |= uint64_t(k[w * 8 + b]) << (8 * b);
+    kw[w] = v;
+  }
+}
+XE_HD uint32_t mo_load_index(const XeMapOp& o, uint32_t i) {
+  const uint8_t* k = o.keys + uint64_t(i) * 4;
+  return uint32_t(k[0]) | uint32_t(k[1]) << 8 | uint32_t(k[2]) << 16 | uint32_t(k[3]) << 24;
+}
+XE_HD bool mo_key_eq(const XeMapOp& o, const uint64_t* r, const uint64_t* kw) {
+  bool eq = true;
+  for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
+    if (k < o.kwords) eq = eq && r[1 + k] == kw[k];
+  return eq;
+}
+// The last-writer word of a slot: the high half of a HASH record's word 0 (little endian), an ARRAY map's
+// word per index. The host build goes through the 64-bit word (one type per object).
+XE_HD uint32_t mo_hi_get(const XeMapOp& o, uint32_t slot) {
+  if (o.kind == XE_DM_ARRAY) return o.win[slot];
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __hip_atomic_load(reinterpret_cast<uint32_t*>(o.recs + uint64_t(slot) * o.rwords) + 1, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+#else
+  return uint32_t(o.recs[uint64_t(slot) * o.rwords] >> 32);
+#endif
+}
+XE_HD void mo_hi_max(const XeMapOp& o, uint32_t slot, uint32_t v) {
+  if (o.kind == XE_DM_ARRAY) { mo_max32(o.win + slot, v); return; }
+#if defined(__HIP_DEVICE_COMPILE__)
+  mo_max32(reinterpret_cast<uint32_t*>(o.recs + uint64_t(slot) * o.rwords) + 1, v);
+#else
+  uint64_t* r = o.recs + uint64_t(slot) * o.rwords;
+  if (uint32_t(*r >> 32) < v) *r = (*r & 0xffffffffull) | (uint64_t(v) << 32);
+#endif
+}
+
+// The walk of xe_interp.h hash_find, one record at a time: first record that is FULL and holds the key;
+// the chain ends at a record that is neither FULL nor a tombstone. kMoAbsent: not there.
+XE_HD uint32_t mo_find(const XeMapOp& o, const uint64_t* kw) {
+  if (o.key_size == 0) return (uint32_t(o.recs[uint64_t(o.cap) * o.rwords]) & XE_SLOT_FULL) ? o.cap : kMoAbsent;
+  const uint32_t mask = o.cap - 1;
+  uint32_t idx = uint32_t(xe_hash_words(kw, o.kwords, o.key_size)) & mask;
+  for (uint32_t probe = 0; probe < o.cap; probe++) {
+    const uint64_t* r = o.recs + uint64_t(idx) * o.rwords;
+    const uint32_t st = uint32_t(r[0]);
+    if (st & XE_SLOT_FULL) {
+      if (mo_key_eq(o, r, kw)) return idx;
+    } else if (!(st & XE_SLOT_TOMB)) {
+      return kMoAbsent;
+    }
+    idx = (idx + 1) & mask;
+  }
+  return kMoAbsent;
+}
+
+// ---------------------------------------------------------------- cooperative value moves
+// Lane `sub` of `lanes` moves its share of len bytes: in units of the widest of 16, 8 or 4 bytes at which
+// source and destination are aligned alike (bytes up to the first aligned address, units, bytes), else
+// bytes. src null: zero fill.
+template <class U>
+XE_HD void mo_move_units(uint8_t* t, const uint8_t* s, uint32_t len, uint32_t sub, uint32_t lanes) {
+  uint32_t head = uint32_t(-uintptr_t(t)) & uint32_t(sizeof(U) - 1);
+  head = head < len ? head : len;
+  for (uint32_t j = sub; j < head; j += lanes) t[j] = s ? s[j] : uint8_t(0);
+  const uint32_t units = (len - head) / uint32_t(sizeof(U));
+  U* tv = reinterpret_cast<U*>(t + head);
+  const U* sv = s ? reinterpret_cast<const U*>(s + head) : nullptr;
+  for (uint32_t j = sub; j < units; j += lanes) tv[j] = s ? sv[j] : U{};
+  for (uint32_t j = head + units * uint32_t(sizeof(U)) + sub; j < len; j += lanes) t[j] = s ? s[j] : uint8_t(0);
+}
+struct alignas(16) XeMo16 { uint64_t a, b; };
+XE_HD void mo_move(uint8_t* t, const uint8_t* s, uint32_t len, uint32_t sub, uint32_t lanes) {
+  const uintptr_t x = s ? (uintptr_t(s) ^ uintptr_t(t)) : 0;
+  if (len >= 16 && !(x & 15)) mo_move_units<XeMo16>(t, s, len, sub, lanes);
+  else if (len >= 8 && !(x & 7)) mo_move_units<uint64_t>(t, s, len, sub, lanes);
+  else if (len >= 4 && !(x & 3)) mo_move_units<uint32_t>(t, s, len, sub, lanes);
+  else
+    for (uint32_t j = sub; j < len; j += lanes) t[j] = s ? s[j] : uint8_t(0);
+}
+
+// ---------------------------------------------------------------- lookup / delete: find
+// Entry i's slot, read-only (kMoAbsent: absent or out of range).
+XE_HD uint32_t mo_slot_of(const XeMapOp& o, uint32_t i) {
+  if (o.kind == XE_DM_ARRAY) {
+    const uint32_t idx = mo_load_index(o, i);
+    return idx < o.max_entries ? idx : kMoAbsent;
+  }
+  uint64_t kw[XE_MAX_KEY / 8];
+  mo_load_key(o, i, kw);
+  return mo_find(o, kw);
+}
+// ... and what follows from it: found[i], slot[i], and a small value on the same lane.
+XE_HD void mo_find_finish(const XeMapOp& o, uint32_t i, uint32_t s, bool with_value) {
+  uint32_t w = s;
+  if (s != kMoAbsent && o.kind == XE_DM_HASH && (uint32_t(o.recs[uint64_t(s) * o.rwords]) & XE_SLOT_VLEN0)) w |= kMoVlen0;
+  o.slot[i] = w;
+  if (o.found) o.found[i] = s != kMoAbsent ? 1 : 0;
+  if (with_value && o.value_size <= kMoInline && o.value_size) {
+    const bool zero = s == kMoAbsent || (w & kMoVlen0);
+    mo_move(o.values_out + uint64_t(i) * o.value_size, zero ? nullptr : o.vals + uint64_t(s) * o.value_size, o.value_size, 0, 1);
+  }
+}
+XE_HD void mo_lookup_value_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint32_t lanes) {
+  const uint32_t w = o.slot[i], s = w & kMoSlotMask;
+  const bool zero = s == kMoAbsent || (w & kMoVlen0);
+  mo_move(o.values_out + uint64_t(i) * o.value_size, zero ? nullptr : o.vals + uint64_t(s) * o.value_size, o.value_size, sub, lanes);
+}
+
+// ---------------------------------------------------------------- update
+// Entry i's record: the one holding its key, or one claimed for it (see the head of this file). True: this
+// entry made the claim (the caller counts them). No free record: kMoErrFull.
+XE_HD bool mo_update_locate_item(const XeMapOp& o, uint32_t i) {
+  if (o.kind == XE_DM_ARRAY) {
+    const uint32_t idx = mo_load_index(o, i);
+    if (idx >= o.max_entries) mo_or32(o.ctr + kMoErr, kMoErrRange);
+    o.slot[i] = idx < o.max_entries ? idx : kMoAbsent;
+    return false;
+  }
+  uint64_t kw[XE_MAX_KEY / 8];
+  mo_load_key(o, i, kw);
+  const uint64_t own = XE_SLOT_BUSY | ((uint64_t(i) + 1) << 32);
+  const bool single = o.key_size == 0;  // the empty key: the one record past the table
+  const uint32_t mask = o.cap - 1;
+  uint32_t idx = single ? o.cap : uint32_t(xe_hash_words(kw, o.kwords, o.key_size)) & mask;
+  for (uint32_t probe = 0; probe < o.cap;) {
+    uint64_t* r = o.recs + uint64_t(idx) * o.rwords;
+    const uint64_t w0 = mo_load64(r);
+    const uint32_t st = uint32_t(w0);
+    if (st & XE_SLOT_FULL) {
+      if (mo_key_eq(o, r, kw)) { o.slot[i] = idx; return false; }
+    } else if (st & XE_SLOT_TOMB) {  // holds key words: a deleted entry or an unused reservation
+      if (mo_key_eq(o, r, kw)) {
+        if (st & XE_SLOT_BUSY) { o.slot[i] = idx; return false; }  // a repetition of this key claimed it
+        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) { o.slot[i] = idx | kMoFresh; return true; }
+        continue;  // lost it (to a repetition of this key): look again
+      }
+    } else if (st & XE_SLOT_BUSY) {  // claimed in this launch by the batch entry it names
+      uint64_t kj[XE_MAX_KEY / 8];
+      const uint32_t j = uint32_t(w0 >> 32) - 1;
+      bool eq = j < o.n;
+      if (eq) {
+        mo_load_key(o, j, kj);
+        for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++) eq = eq && kj[k] == kw[k];
+      }
+      if (eq) { o.slot[i] = idx; return false; }
+    } else {  // free
+      if (mo_cas64(r, w0, own) == w0) { o.slot[i] = idx | kMoFresh; return true; }
+      continue;  // lost it: look again
+    }
+    if (single) break;
+    idx = (idx + 1) & mask;
+    probe++;
+  }
+  mo_or32(o.ctr + kMoErr, kMoErrFull);
+  o.slot[i] = kMoAbsent;
+  return false;
+}
+// The claim of entry i put back: a free record is free again (its key words were never written), a
+// tombstone is the tombstone it was.
+XE_HD void mo_update_undo_item(const XeMapOp& o, uint32_t i) {
+  const uint32_t w = o.slot[i];
+  if (o.kind != XE_DM_HASH || !(w & kMoFresh)) return;
+  uint64_t* r = o.recs + uint64_t(w & kMoSlotMask) * o.rwords;
+  r[0] = uint64_t(uint32_t(r[0]) & ~XE_SLOT_BUSY);
+}
+XE_HD void mo_update_mark_item(const XeMapOp& o, uint32_t i) {
+  const uint32_t w = o.slot[i], s = w & kMoSlotMask;
+  if (o.kind == XE_DM_HASH && (w & kMoFresh)) {
+    uint64_t* r = o.recs + uint64_t(s) * o.rwords;
+    if (!(uint32_t(r[0]) & XE_SLOT_TOMB)) {  // claimed free: the key words are this entry's to write
+      uint64_t kw[XE_MAX_KEY / 8];
+      mo_load_key(o, i, kw);
+      for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
+        if (k < o.kwords) r[1 + k] = kw[k];
+    }
+  }
+  mo_hi_max(o, s, i + 1);
+  if (i == 0 && o.kind == XE_DM_HASH) *o.count += o.ctr[kMoNew];
+}
+XE_HD void mo_update_copy_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint32_t lanes) {
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (mo_hi_get(o, s) != i + 1) return;  // a later repetition of the key writes the value (or has written it)
+  const uint8_t* v = o.values_in + uint64_t(i) * o.value_size;
+  mo_move(o.vals + uint64_t(s) * o.value_size, v, o.value_size, sub, lanes);
+  mo_move(o.snap + uint64_t(s) * o.value_size, v, o.value_size, sub, lanes);
+  if (sub == 0) {
+    if (o.kind == XE_DM_HASH) o.recs[uint64_t(s) * o.rwords] = XE_SLOT_FULL;
+    else o.win[s] = 0;
+  }
+}
+
+// ---------------------------------------------------------------- delete
+XE_HD void mo_delete_claim_item(const XeMapOp& o, uint32_t i) {
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (s == kMoAbsent) return;
+  uint64_t* r = o.recs + uint64_t(s) * o.rwords;
+  const uint64_t w0 = mo_load64(r);
+  if (!(uint32_t(w0) & XE_SLOT_FULL)) return;  // a repetition of the key has it
+  if (mo_cas64(r, w0, XE_SLOT_TOMB | ((uint64_t(i) + 1) << 32)) == w0) mo_add32(o.ctr + kMoGone, 1);
+}
+XE_HD void mo_delete_zero_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint32_t lanes) {
+  if (i == 0 && sub == 0) *o.count -= o.ctr[kMoGone];
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (s == kMoAbsent) return;
+  if (mo_hi_get(o, s) != i + 1) return;
+  mo_move(o.vals + uint64_t(s) * o.value_size, nullptr, o.value_size, sub, lanes);
+  mo_move(o.snap + uint64_t(s) * o.value_size, nullptr, o.value_size, sub, lanes);
+  if (sub == 0) o.recs[uint64_t(s) * o.rwords] = XE_SLOT_TOMB;  // a plain tombstone, its key words kept
+}
+
+#ifndef XE_HOSTSIM
+extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
+#else
+// The host simulation: the same items, one after another.
+static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
+  const XeMapOp& o = *op;
+  for (uint32_t i = 0; i < o.n; i++) {
+    switch (step) {
+      case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i), true); break;
+      case XE_MO_LOOKUP_VALUE: mo_lookup_value_item(o, i, 0, 1); break;
+      case XE_MO_UPDATE_LOCATE: if (mo_update_locate_item(o, i)) o.ctr[kMoNew]++; break;
+      case XE_MO_UPDATE_UNDO: mo_update_undo_item(o, i); break;
+      case XE_MO_UPDATE_MARK: mo_update_mark_item(o, i); break;
+      case XE_MO_UPDATE_COPY: mo_update_copy_item(o, i, 0, 1); break;
+      case XE_MO_DELETE_FIND: mo_find_finish(o, i, mo_slot_of(o, i), false); break;
+      case XE_MO_DELETE_CLAIM: mo_delete_claim_item(o, i); break;
+      case XE_MO_DELETE_ZERO: mo_delete_zero_item(o, i, 0, 1); break;
+      default: return -1;
+    }
+  }
+  return 0;
+}
+#endif
+#endif  // XE_MAPOPS_H

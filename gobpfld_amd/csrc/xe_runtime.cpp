@@ -9,6 +9,7 @@
 // Built twice: with hipcc into gobpfld_amd/libxdpemu.so (the product), and with g++ -DXE_HOSTSIM
 // into tests/hostsim/ (CPU-only test build of the same logic; never loaded by the product).
 #include "xe_internal.h"
+#include "xe_mapops.h"
 
 #include <algorithm>
 #include <map>
@@ -733,6 +734,8 @@ struct HostMap {
   uint32_t ewclass = 0; // width classes of the adds since xe_epoch_begin
   uint8_t* d_ebase = nullptr;  // values at xe_epoch_begin (the epoch's delta base)
   uint32_t live = 0;    // HASH: entry count for replica sizing (host count, refreshed after ordered runs)
+  uint32_t* d_win = nullptr;  // ARRAY: the batched device update's last-writer words (xe_mapops.h), zero between calls
+  uint64_t uploads = 0, downloads = 0;  // whole-map transfers so far (xe_debug_map_traffic)
   bool host_dirty = true, dev_dirty = false;
   // ordered maps (LRU_HASH / QUEUE / STACK / PERF_EVENT_ARRAY): the host mirror in Go order —
   // LRU: the UsageList (most recently used first) with each key's value; QUEUE / STACK: the Values
@@ -995,6 +998,12 @@ struct xe_vm {
   void* d_relink = nullptr; size_t d_relink_cap = 0;  // lru_relink: sort keys / values + scratch
   uint64_t lru_epoch = 0;  // runs so far: LRU stamps carry it in their top bits (header word 5)
   uint32_t sched = 0;  // chunk -> wave schedule permutation of the parallel passes (xe_debug_set_schedule)
+  // batched device map operations (xe_mapops.h): per-entry slots + counters, and the staging buffers of
+  // the host-pointer forms
+  void* d_mo = nullptr; size_t d_mo_cap = 0;
+  void* d_mo_keys = nullptr; size_t d_mo_keys_cap = 0;
+  void* d_mo_vals = nullptr; size_t d_mo_vals_cap = 0;
+  void* d_mo_found = nullptr; size_t d_mo_found_cap = 0;
 };
 // ---- keyed ordered execution buffers (XeKeyed), sized for n packets
 static void keyed_free(xe_vm* vm) {
@@ -1143,6 +1152,8 @@ void map_free_device(HostMap& m) {
   for (auto& p : m.d_asnap) { dev_free(p); p = nullptr; }
   dev_free(m.d_ebase);
   m.d_ebase = nullptr;
+  dev_free(m.d_win);
+  m.d_win = nullptr;
   dev_free(m.d_vals); dev_free(m.d_snap); dev_free(m.d_keys); dev_free(m.d_state); dev_free(m.d_count); dev_free(m.d_rep);
   m.d_vals = m.d_snap = nullptr; m.d_keys = nullptr; m.d_state = m.d_count = nullptr; m.d_rep = nullptr;
   dev_free(m.d_hdr); dev_free(m.d_link); dev_free(m.d_elen); dev_free(m.d_rec);
@@ -1246,6 +1257,7 @@ int map_upload(xe_vm* vm, HostMap& m) {
   if (dsync(vm->stream)) return -1;
   m.host_dirty = false;
   m.live = m.count;
+  m.uploads++;
   return 0;
 }
 
@@ -1355,6 +1367,7 @@ int map_download(xe_vm* vm, HostMap& m) {
   if (dsync(vm->stream)) return -1;
   m.dev_dirty = false;
   m.live = m.count;
+  m.downloads++;
   if (m.dkind == XE_DM_HASH && m.drop_tombstones()) m.host_dirty = true;  // the device gets the clean layout
   return 0;
 }
@@ -1736,6 +1749,7 @@ void xe_destroy(xe_vm* vm) {
   dev_free(vm->d_arena_par); dev_free(vm->d_arena_seq); dev_free(vm->d_ksnap);
   dev_free(vm->d_umem); dev_free(vm->d_desc); dev_free(vm->d_res); dev_free(vm->d_ver); dev_free(vm->d_regs);
   dev_free(vm->d_usnap); dev_free(vm->d_ovl); dev_free(vm->d_app); dev_free(vm->d_app_sort); dev_free(vm->d_relink);
+  dev_free(vm->d_mo); dev_free(vm->d_mo_keys); dev_free(vm->d_mo_vals); dev_free(vm->d_mo_found);
   keyed_free(vm);
   vm->t0.fini(); vm->t1.fini(); vm->t2.fini();
 #ifndef XE_HOSTSIM
@@ -4124,6 +4138,205 @@ int xe_map_state_import(xe_vm* vm, int32_t mi, const void* d_in, void* stream) {
   return XE_OK;
 }
 
+}  // extern "C"
+
+// ---- batched map operations on the device copy (xe_mapops.h / xe_mapops.hip)
+namespace {
+constexpr uint64_t kMoMaxCount = 1ull << 31;
+
+// Common start of the three calls: pipelined batches complete, the map is of a served kind and current on
+// the device, the per-entry scratch holds `count` slots behind zeroed counters. 1: nothing to do (count 0).
+int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, HostMap** mp, XeMapOp* op, xe_stream_t* sp) {
+  if (!vm) return XE_ERR_INVAL;
+  if (int rc = xe_sync(vm)) return rc;
+  HostMap* m = get_map(vm, mi);
+  if (!m) return fail(vm, XE_ERR_INVAL, "map index out of bounds");
+  if (m->ordered() || (m->dkind != XE_DM_ARRAY && m->dkind != XE_DM_HASH))
+    return fail(vm, XE_ERR_UNSUPPORTED, "batched device map operations serve ARRAY and HASH maps only");
+  if (m->dkind == XE_DM_ARRAY && m->def.max_entries >= kMoAbsent)
+    return fail(vm, XE_ERR_UNSUPPORTED, "batched device map operations: ARRAY map too large");
+  if (writes && vm->epoch_open) return fail(vm, XE_ERR_INVAL, "map writes are refused while a shard epoch is open");
+  if (count > kMoMaxCount) return fail(vm, XE_ERR_INVAL, "batched map operation: more than 2^31 keys");
+  if (set_device(vm->settings.device)) return fail(vm, XE_ERR_DEVICE, "hipSetDevice failed");
+  xe_stream_t s = stream ? (xe_stream_t)stream : vm->stream;
+  *mp = m;
+  *sp = s;
+  if (!count) return 1;
+  if (m->host_dirty) {
+    vm->staged_slot = -1;  // the device values change under the staged snapshots
+    if (map_upload(vm, *m)) return fail(vm, XE_ERR_DEVICE, "map upload");
+  }
+  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(count) * 4) || dmemset(vm->d_mo, 0, kMoCounters * 4, s))
+    return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  XeMapOp o{};
+  o.kind = m->dkind;
+  o.key_size = m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size;
+  o.value_size = m->def.value_size;
+  o.max_entries = m->def.max_entries;
+  o.cap = m->cap;
+  o.kwords = m->kwords;
+  o.rwords = m->dkind == XE_DM_HASH ? xe_hash_rwords(m->kwords) : 0;
+  o.n = uint32_t(count);
+  o.recs = m->d_keys;
+  o.vals = m->d_vals;
+  o.snap = m->d_snap;
+  o.count = m->d_count;
+  o.ctr = (uint32_t*)vm->d_mo;
+  o.slot = o.ctr + kMoCounters;
+  *op = o;
+  return XE_OK;
+}
+int mapop_steps(xe_vm* vm, const XeMapOp& o, std::initializer_list<uint32_t> steps, xe_stream_t s) {
+  for (uint32_t st : steps)
+    if (xe_launch_mapop(&o, st, (void*)s)) return fail(vm, XE_ERR_DEVICE, "map operation launch");
+  return XE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int xe_map_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_values, void* d_found,
+                               void* stream) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, false, stream, &m, &o, &s);
+  if (rc < 0) return rc;
+  if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
+  if (rc == 1) return XE_OK;
+  o.keys = (const uint8_t*)d_keys;
+  o.values_out = (uint8_t*)d_values;
+  o.found = (uint8_t*)d_found;
+  if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
+  if (o.value_size > kMoInline)
+    if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map lookup batch");
+  return XE_OK;
+}
+
+int xe_map_update_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, const void* d_values, uint64_t count, void* stream) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, true, stream, &m, &o, &s);
+  if (rc < 0) return rc;
+  if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
+  if (rc == 1) return XE_OK;
+  o.keys = (const uint8_t*)d_keys;
+  o.values_in = (const uint8_t*)d_values;
+  if (m->dkind == XE_DM_ARRAY && !m->d_win) {
+    if (dev_alloc((void**)&m->d_win, size_t(std::max<uint32_t>(m->def.max_entries, 1)) * 4) ||
+        dmemset(m->d_win, 0, size_t(std::max<uint32_t>(m->def.max_entries, 1)) * 4, s))
+      return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  }
+  o.win = m->d_win;
+  uint32_t ctr[kMoCounters], cnt = 0;
+  for (int attempt = 0;; attempt++) {
+    if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_LOCATE}, s)) return r;
+    if (d2h(ctr, o.ctr, sizeof ctr, s) || (m->dkind == XE_DM_HASH && d2h(&cnt, m->d_count, 4, s)) || dsync(s))
+      return fail(vm, XE_ERR_DEVICE, "map update batch");
+    const bool range = ctr[kMoErr] & kMoErrRange, full = ctr[kMoErr] & kMoErrFull;
+    const bool fits = m->dkind != XE_DM_HASH || uint64_t(cnt) + ctr[kMoNew] <= m->def.max_entries;
+    if (!range && !full && fits) break;
+    if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_UNDO}, s)) return r;
+    if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
+    if (m->dkind == XE_DM_HASH) m->dev_dirty = true;  // claims were written and put back: the mirror reads the device again
+    if (range) return fail(vm, XE_ERR_INVAL, "key out of range");
+    if (!fits || attempt) return fail(vm, XE_ERR_NOMEM, "map is full");
+    // The keys fit under max_entries but a probe chain found no free record: deletes and unused keyed
+    // reservations have left tombstones in all of them. One visit to the host mirror rebuilds the table
+    // without them (map_download: drop_tombstones); then the batch is located again.
+    m->dev_dirty = true;
+    vm->staged_slot = -1;
+    if (map_download(vm, *m) || (m->host_dirty && map_upload(vm, *m))) return fail(vm, XE_ERR_DEVICE, "map compaction");
+    if (dmemset(vm->d_mo, 0, kMoCounters * 4, s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
+  }
+  if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY}, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
+  if (m->dkind == XE_DM_HASH) m->live = cnt + ctr[kMoNew];
+  m->dev_dirty = true;
+  vm->staged_slot = -1;  // the device values changed under the staged snapshots
+  return XE_OK;
+}
+
+int xe_map_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_found, void* stream) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const int rc = mapop_begin(vm, mi, d_keys ? count : 0, true, stream, &m, &o, &s);
+  if (rc < 0) return rc;
+  if (m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
+  if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
+  if (rc == 1) return XE_OK;
+  o.keys = (const uint8_t*)d_keys;
+  o.found = (uint8_t*)d_found;
+  if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO}, s)) return r;
+  uint32_t cnt = 0;
+  if (d2h(&cnt, m->d_count, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map delete batch");
+  m->live = cnt;
+  m->dev_dirty = true;
+  vm->staged_slot = -1;
+  return XE_OK;
+}
+
+// Host-pointer forms: stage, run the device form on the VM's stream, copy back.
+int xe_map_lookup_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, void* values, uint8_t* found) {
+  if (!vm) return XE_ERR_INVAL;
+  HostMap* m = get_map(vm, mi);
+  if (!m || !count || !keys || !values || count > kMoMaxCount)
+    return xe_map_lookup_batch_device(vm, mi, keys, count, values, found, nullptr);  // its checks, its answer
+  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size), vb = size_t(count) * m->def.value_size;
+  set_device(vm->settings.device);
+  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb) ||
+      ensure_buf(&vm->d_mo_found, &vm->d_mo_found_cap, size_t(count)) || h2d(vm->d_mo_keys, keys, kb, vm->stream) ||
+      dsync(vm->stream))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (int rc = xe_map_lookup_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_vals, vm->d_mo_found, nullptr)) return rc;
+  if ((vb && d2h(values, vm->d_mo_vals, vb, vm->stream)) || (found && d2h(found, vm->d_mo_found, size_t(count), vm->stream)) ||
+      dsync(vm->stream))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  return XE_OK;
+}
+
+int xe_map_update_batch_staged(xe_vm* vm, int32_t mi, const void* keys, const void* values, uint64_t count) {
+  if (!vm) return XE_ERR_INVAL;
+  HostMap* m = get_map(vm, mi);
+  if (!m || !count || !keys || !values || count > kMoMaxCount)
+    return xe_map_update_batch_device(vm, mi, keys, values, count, nullptr);
+  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size), vb = size_t(count) * m->def.value_size;
+  set_device(vm->settings.device);
+  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb) ||
+      h2d(vm->d_mo_keys, keys, kb, vm->stream) || (vb && h2d(vm->d_mo_vals, values, vb, vm->stream)) || dsync(vm->stream))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  return xe_map_update_batch_device(vm, mi, vm->d_mo_keys, vm->d_mo_vals, count, nullptr);
+}
+
+int xe_map_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, uint8_t* found) {
+  if (!vm) return XE_ERR_INVAL;
+  HostMap* m = get_map(vm, mi);
+  if (!m || !count || !keys || count > kMoMaxCount) return xe_map_delete_batch_device(vm, mi, keys, count, found, nullptr);
+  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size);
+  set_device(vm->settings.device);
+  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ensure_buf(&vm->d_mo_found, &vm->d_mo_found_cap, size_t(count)) ||
+      h2d(vm->d_mo_keys, keys, kb, vm->stream) || dsync(vm->stream))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (int rc = xe_map_delete_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_found, nullptr)) return rc;
+  if (found && (d2h(found, vm->d_mo_found, size_t(count), vm->stream) || dsync(vm->stream)))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  return XE_OK;
+}
+
+int xe_debug_map_traffic(xe_vm* vm, int32_t mi, uint64_t* uploads, uint64_t* downloads) {
+  HostMap* m = get_map(vm, mi);
+  if (!m) return XE_ERR_INVAL;
+  if (uploads) *uploads = m->uploads;
+  if (downloads) *downloads = m->downloads;
+  return XE_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 int xe_debug_set_schedule(xe_vm* vm, uint32_t sched) {
   if (!vm) return XE_ERR_INVAL;
   if (int rc = xe_sync(vm)) return rc;

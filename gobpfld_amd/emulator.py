@@ -253,6 +253,82 @@ class VM:
         self._check(self.lib.map_count(self.h, m, C.byref(n)), "map count")
         return int(n.value)
 
+    # ---- batched map access on the device copy (ARRAY / HASH; xe_map_*_batch_device). Keys and values
+    # are uint8 numpy arrays, staged through the VM's device buffers, or CUDA tensors, whose device
+    # addresses are passed through (the results are then tensors on the same device).
+    @staticmethod
+    def _is_dev(x) -> bool:
+        return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
+
+    def _mo_keys(self, m: int, keys):
+        d = self.map_defs[m]
+        ks = 4 if d.type in ARRAY_TYPES else d.key_size  # (list maps: the library refuses them)
+        if self._is_dev(keys):
+            import torch
+            k = keys.contiguous().view(torch.uint8).reshape(-1)
+            # the calls run on the VM's stream: whatever torch has queued to produce the tensors completes first
+            torch.cuda.current_stream(k.device).synchronize()
+        else:
+            k = np.ascontiguousarray(keys).view(np.uint8).reshape(-1)
+        n = len(k) // ks if ks else len(keys)
+        assert n * ks == len(k), "keys: a whole number of key_size-byte keys"
+        return k, n
+
+    def map_lookup_batch(self, m: int, keys):
+        """(values[n, value_size], found[n]) of n keys, read from the device copy of the map."""
+        d = self.map_defs[m]
+        k, n = self._mo_keys(m, keys)
+        if self._is_dev(k):
+            import torch
+            # (the call writes every byte: no fill kernels on torch's stream that its own stream could overtake)
+            vals = torch.empty((n, d.value_size), dtype=torch.uint8, device=k.device)
+            found = torch.empty(n, dtype=torch.uint8, device=k.device)
+            rc = self.lib.map_lookup_batch_device(self.h, m, k.data_ptr() or None, n, vals.data_ptr() or None,
+                                                  found.data_ptr() or None, None)
+        else:
+            vals = np.zeros((n, d.value_size), dtype=np.uint8)
+            found = np.zeros(n, dtype=np.uint8)
+            rc = self.lib.map_lookup_batch(self.h, m, k.ctypes.data, n, vals.ctypes.data, found.ctypes.data)
+        self._check(rc, "map lookup batch")
+        return vals, found
+
+    def map_update_batch_device(self, m: int, keys, values) -> None:
+        """All-or-nothing update of n keys on the device copy (xe_map_update_batch_device): the result of
+        map_update key by key in order, or an error and an unchanged map."""
+        d = self.map_defs[m]
+        k, n = self._mo_keys(m, keys)
+        if self._is_dev(k):
+            import torch
+            assert self._is_dev(values), "keys and values: both on the device, or both on the host"
+            v = values.contiguous().view(torch.uint8).reshape(-1)
+            assert len(v) == n * d.value_size
+            torch.cuda.current_stream(v.device).synchronize()
+            rc = self.lib.map_update_batch_device(self.h, m, k.data_ptr() or None, v.data_ptr() or None, n, None)
+        else:
+            v = np.ascontiguousarray(values).view(np.uint8).reshape(-1)
+            assert len(v) == n * d.value_size
+            rc = self.lib.map_update_batch_staged(self.h, m, k.ctypes.data, v.ctypes.data, n)
+        self._check(rc, "map update batch (device)")
+
+    def map_delete_batch(self, m: int, keys):
+        """Delete n keys on the device copy; found[n] = the key was present before the call."""
+        k, n = self._mo_keys(m, keys)
+        if self._is_dev(k):
+            import torch
+            found = torch.empty(n, dtype=torch.uint8, device=k.device)
+            rc = self.lib.map_delete_batch_device(self.h, m, k.data_ptr() or None, n, found.data_ptr() or None, None)
+        else:
+            found = np.zeros(n, dtype=np.uint8)
+            rc = self.lib.map_delete_batch(self.h, m, k.ctypes.data, n, found.ctypes.data)
+        self._check(rc, "map delete batch")
+        return found
+
+    def map_traffic(self, m: int) -> tuple[int, int]:
+        """xe_debug_map_traffic: (uploads, downloads) of the whole map so far."""
+        up, down = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.debug_map_traffic(self.h, m, C.byref(up), C.byref(down)), "map traffic")
+        return up.value, down.value
+
     def map_values_bytes(self, m: int) -> int:
         b = C.c_uint64()
         self._check(self.lib.map_values_bytes(self.h, m, C.byref(b)), "map values bytes")

@@ -341,6 +341,49 @@ int xe_map_state_bytes(xe_vm* vm, int32_t map_idx, uint64_t* bytes);
 int xe_map_state_export(xe_vm* vm, int32_t map_idx, void* d_out, void* stream);
 int xe_map_state_import(xe_vm* vm, int32_t map_idx, const void* d_in, void* stream);
 
+/* --- batched map access on the device copy (ARRAY and HASH kinds): lookup, update and delete of `count`
+ * keys by kernels that touch only those keys' records and values. Nothing of the map crosses to the host
+ * or back, where xe_map_lookup / _update / _delete / _count / _dump first bring the whole map to the host
+ * mirror and the next batch uploads it again. Every d_* is a device address (a host address in the
+ * host-simulation build). keys: count x key_size bytes back to back (ARRAY kinds: one u32 index per key);
+ * values: count x value_size bytes back to back; d_found: one u8 per key, may be NULL.
+ *
+ * Each call completes pipelined batches first (xe_sync) and is finished when it returns; stream NULL is
+ * the VM's stream; count 0 does nothing and returns XE_OK; a map changed through the host calls is
+ * uploaded once first. LRU_HASH, QUEUE, STACK and PERF_EVENT_ARRAY maps return XE_ERR_UNSUPPORTED; a NULL
+ * required pointer, or more than 2^31 keys, XE_ERR_INVAL.
+ *
+ *   lookup: d_found[i] = 1 and value i = what xe_map_lookup returns (zeros for an entry whose backing
+ *           became nil); otherwise d_found[i] = 0 and value i is zero-filled. An ARRAY index >=
+ *           max_entries counts as absent. Changes no state.
+ *   update: the result of xe_map_update for i = 0 .. count-1 in order, where that sequence succeeds (a
+ *           key repeated in the batch ends with its last value). ALL OR NOTHING, unlike
+ *           xe_map_update_batch, which keeps the updates made before the first failure: when the
+ *           distinct absent keys do not fit under max_entries the call returns XE_ERR_NOMEM, when an
+ *           ARRAY index is out of range XE_ERR_INVAL, and the map is unchanged.
+ *   delete: HASH kinds only (ARRAY: XE_ERR_INVAL, as xe_map_delete). d_found[i] = the key was present
+ *           before the call, the same for every repetition of a key; afterwards the key is absent.
+ *
+ * Update and delete are refused with XE_ERR_INVAL while a shard epoch is open (xe_epoch_begin). They
+ * write the delta base of xe_map_delta along with the values, so a control-plane write never shows up
+ * as packet adds. The slot layout they leave is valid for every probe but need not be the one the host
+ * calls would have produced (deleted records stay as tombstones until the map next visits the host; a
+ * table whose free records have all become tombstones is compacted through the host once, the only case
+ * in which these calls move the map). It already depends on timing after batches that insert keys;
+ * shards that need equal layouts copy them with xe_map_state_export / _import. */
+int xe_map_lookup_batch_device(xe_vm* vm, int32_t map_idx, const void* d_keys, uint64_t count, void* d_values,
+                               void* d_found, void* stream);
+int xe_map_update_batch_device(xe_vm* vm, int32_t map_idx, const void* d_keys, const void* d_values, uint64_t count,
+                               void* stream);
+int xe_map_delete_batch_device(xe_vm* vm, int32_t map_idx, const void* d_keys, uint64_t count, void* d_found,
+                               void* stream);
+/* The same with host pointers: keys and values are staged through device buffers of the VM (for hosts
+ * that hold no device memory, such as the Go binding). xe_map_update_batch_staged is the all-or-nothing
+ * device update, not xe_map_update_batch. */
+int xe_map_lookup_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t count, void* values, uint8_t* found);
+int xe_map_update_batch_staged(xe_vm* vm, int32_t map_idx, const void* keys, const void* values, uint64_t count);
+int xe_map_delete_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t count, uint8_t* found);
+
 /* --- one process, N devices (SURVEY §8b xe_run_batch_multi): the Go host shards a batch over the
  * GPUs of a node through the FFI alone. vms[k] runs on its own device with identical programs, maps
  * and map contents (the caller sets each up the same way). Exchange over RCCL (xGMI) when the devices
@@ -430,6 +473,9 @@ int xe_debug_set_lru_epoch(xe_vm* vm, uint64_t epoch);
 /* An ordered map's device value pool: its room (value ids) and the next fresh id (LRU_HASH / QUEUE /
  * STACK; PERF: event records). Tests check that a stream of evicting batches keeps the pool's size. */
 int xe_debug_map_pool(xe_vm* vm, int32_t map, uint64_t* room, uint64_t* next_id);
+/* How many times the whole map has been uploaded to / downloaded from the device (the transfers the host
+ * map calls cause; the batched device calls above cause none). */
+int xe_debug_map_traffic(xe_vm* vm, int32_t map_idx, uint64_t* uploads, uint64_t* downloads);
 
 /* build / device info */
 const char* xe_version(void);
