@@ -6,6 +6,7 @@
 // packets in order in sequential mode (exact fallback for order-dependent map effects). xe_delta_kernel / xe_apply_delta_kernel: u64 counter deltas for
 // the multi-GPU all-reduce.
 #include "xe_interp.h"
+#include "xe_kernels.h"
 
 #include <hipcub/device/device_radix_sort.hpp>
 #include <hipcub/device/device_scan.hpp>

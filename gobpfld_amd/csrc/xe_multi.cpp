@@ -11,6 +11,7 @@
 // VMs that share a device (a one-GPU test of this path) exchange through device kernels instead of
 // RCCL, which refuses duplicate devices in one communicator.
 #include "xe_internal.h"
+#include "xe_kernels.h"  // the xe_internal_* hooks of xe_runtime.cpp
 
 #include <cstring>
 #include <string>
@@ -21,16 +22,6 @@
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #endif
-
-// internal hooks of xe_runtime.cpp
-extern "C" int xe_internal_vm_device(const xe_vm* vm);
-extern "C" void* xe_internal_vm_stream(xe_vm* vm);
-extern "C" int xe_internal_nmaps(const xe_vm* vm);
-extern "C" int xe_internal_may_write_packet(const xe_vm* vm);
-extern "C" int xe_internal_delta_sum(xe_vm* vm, void* acc, const void* in, uint64_t bytes, uint32_t lane);
-extern "C" int xe_internal_alloc(xe_vm* vm, void** p, uint64_t bytes);
-extern "C" void xe_internal_free(xe_vm* vm, void* p);
-extern "C" int xe_internal_copy(xe_vm* vm, void* dst, const void* src, uint64_t bytes);
 
 struct xe_multi {
   std::vector<xe_vm*> vms;

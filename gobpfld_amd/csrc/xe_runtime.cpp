@@ -31,42 +31,8 @@ typedef void* xe_stream_t;
 #else
 #include <hip/hip_runtime_api.h>
 typedef hipStream_t xe_stream_t;
-extern "C" int xe_launch_interp(const XeParams* P, uint32_t blocks, uint32_t threads, hipStream_t s);
-extern "C" int xe_launch_delta(const void* cur, const void* snap, void* out, uint64_t bytes, uint32_t lane, hipStream_t s);
-extern "C" int xe_launch_apply_delta(void* cur, const void* snap, const void* delta, uint64_t bytes, uint32_t lane,
-                                     hipStream_t s);
-extern "C" int xe_launch_rep_fold(void* vals, void* rep, uint64_t stride_words, uint32_t nrep, uint64_t nwords,
-                                  const void* recs, uint32_t rwords, uint32_t vsize, uint32_t cap, const void* lim, hipStream_t s);
-extern "C" int xe_launch_delta_sum(void* acc, const void* in, uint64_t bytes, uint32_t lane, hipStream_t s);
-extern "C" int xe_launch_prologue(const void* const* src, void* const* dst, const uint64_t* words, uint32_t nseg,
-                                  void* zero, uint64_t zero_words, hipStream_t s);
-extern "C" int xe_launch_tail(const XeTailArgs* A, hipStream_t s);
-extern "C" int xe_launch_desc_overlap(const void* desc, uint32_t n, uint64_t umem_len, void* scratch, size_t* scratch_bytes,
-                                      uint32_t* flag, hipStream_t s);
-extern "C" void* xe_jit_get(const XeUop* const* progs, const uint32_t* lens, uint32_t nprogs, int32_t entry, int device,
-                            const XeDevMap* maps, uint32_t nmaps, bool* cyclic, bool* general, const char** err, int keyed, uint64_t* maxpath);
-extern "C" int xe_launch_keyed(const XeKeyed* K, const XeDevMap* maps, uint8_t* skip, uint32_t step, uint32_t items,
-                               hipStream_t s);
-extern "C" int xe_launch_keyed_sort(const XeKeyed* K, uint32_t n, uint32_t end_bit, void* scratch, size_t* bytes, hipStream_t s);
-extern "C" int xe_launch_keyed_esort(const XeKeyed* K, void* scratch, size_t* bytes, hipStream_t s);
-extern "C" int xe_launch_append(const XeAppendArgs* A, uint32_t end_bit, void* scratch, size_t* bytes, hipStream_t s);
-extern "C" int xe_launch_keyed_scan(const XeKeyed* K, uint32_t n, void* scratch, size_t* bytes, hipStream_t s);
-extern "C" int xe_launch_pop(const uint32_t* src, uint32_t* dst, uint32_t n, uint32_t mode, uint32_t arg, XePopSlots sl,
-                             uint32_t* flag, hipStream_t s);
-extern "C" int xe_launch_lru_relink(uint64_t* tag, uint32_t pool, uint32_t cnt, uint32_t* link, uint64_t* hdr, void* scratch,
-                                    size_t* bytes, int renumber, hipStream_t s);
-extern "C" int xe_launch_lru_tag_fold(uint64_t* tag, uint64_t* rep, uint32_t pool, uint32_t r, const uint64_t* hdr, hipStream_t s);
-extern "C" int xe_launch_lru_log(const uint64_t* tag, uint32_t pool, const uint32_t* order, const uint64_t* hdr, uint64_t* log,
-                                 hipStream_t s);
-extern "C" int xe_jit_launch(void* fn, const XeParams* P, uint32_t blocks, uint32_t threads, hipStream_t s);
-extern "C" int xe_jit_occupancy(void* fn, uint32_t nmaps);
-extern "C" int xe_interp_occupancy(uint32_t nmaps);
 #endif
-
-// the kernel generator (xe_jit.cpp; in the host simulation too: sources only, no compiles)
-extern "C" int xe_jit_may_write_entries(const XeUop* prog, size_t n);
-extern "C" size_t xe_jit_source_for(const XeUop* const* progs, const uint32_t* lens, uint32_t nprogs, int32_t entry,
-                                    const XeDevMap* maps, uint32_t nmaps, int keyed, char* buf, size_t buflen);
+#include "xe_kernels.h"  // the launchers of xe_kernel.hip, the kernel generator of xe_jit.cpp, xe_multi.cpp's hooks
 
 #define XE_FRAME_SIZE 256  // DefaultVMSettings().StackFrameSize (emulator/vm.go:291-296)
 
@@ -461,6 +427,10 @@ int cu_count(int dev) {
   return n;
 }
 #endif
+// the emulator kernel of a batch: the per-program kernel `fn`, or the interpreter when there is none
+int launch_emulator(void* fn, const XeParams* P, uint32_t blocks, uint32_t threads, xe_stream_t s) {
+  return fn ? launch_jit(fn, P, blocks, threads, s) : launch_interp(P, blocks, threads, s);
+}
 
 // ------------------------------------------------------------------ decoder + translator
 int size_log2(uint8_t sizecode) {  // ebpf.Size: W=0x00, H=0x08, B=0x10, DW=0x18 (ebpf/ebpf.go:106-116)
@@ -908,13 +878,13 @@ struct xe_vm {
   uint64_t jit_maxpath = 0;  // acyclic kernels: the most instructions a packet can execute
   bool jit_general = false;  // the per-program kernel uses the general lane model (loops, > 57 objects)
   std::string jit_error;
-  // its keyed variant (keyed ordered execution), built with it when the program may write map entries
-  void* kjit_fn = nullptr;
-  void* ljit_fn = nullptr;   // the verdict-only variant (no result / register records)
-  bool ljit_ready = false;
-  void* sjit_fn = nullptr;   // the scalar one-lane replay (xe_jit.cpp XE_JV_SEQ)
-  bool sjit_ready = false;
-  bool kjit_ready = false;
+  // its variants (xe_jit.cpp: 1 keyed ordered execution, 2 verdict-only, 3 the scalar one-lane replay),
+  // each built on first use (variant_kernel) and reset with the kernel (select_engine); index 0 unused
+  struct Variant {
+    bool ready = false;
+    void* fn = nullptr;
+  };
+  std::array<Variant, 4> jit_variants{};
   Timer t0, t1, t2;
   // room the ordered maps' device copies keep for one run (elements / events, event bytes), grown
   // ×4 when a run reports XE_FLAG_CAPACITY
@@ -2382,6 +2352,10 @@ static int ensure_arena(xe_vm* vm, bool seq, uint32_t nl, XeGen& g) {
   return 0;
 }
 
+}  // extern "C"
+
+// ---- running batches: internal to this file, C++ linkage (inside the extern "C" block above, the helpers of
+// an anonymous namespace were exported under their bare names)
 namespace {
 
 // The helper table differs from LinuxHelperFunctions (xe_set_helper) or a trace is configured: both live in
@@ -2473,12 +2447,7 @@ int select_engine(xe_vm* vm, void*& jit, bool& jit_general) {
       vm->jit_idx = vm->entry;
       vm->jit_nmaps = vm->maps.size();
       vm->jit_nprogs = vm->programs.size();
-      vm->kjit_ready = false;
-      vm->kjit_fn = nullptr;
-      vm->ljit_ready = false;
-      vm->ljit_fn = nullptr;
-      vm->sjit_ready = false;
-      vm->sjit_fn = nullptr;
+      vm->jit_variants = {};
     }
     jit = vm->jit_fn;
     jit_general = vm->jit_general;
@@ -2490,69 +2459,35 @@ int select_engine(xe_vm* vm, void*& jit, bool& jit_general) {
   return XE_OK;
 }
 
-// The keyed variant of the selected per-program kernel (null: the interpreter runs the keyed passes,
-// or the variant cannot be built). Built once per kernel, ahead of the batch that first needs it
-// (xe_prepare, or the start of a run whose program may write map entries), so no batch's device time
-// includes a compile.
-void* keyed_kernel(xe_vm* vm, void* jit) {
-#ifndef XE_HOSTSIM
-  if (!jit) return nullptr;
-  if (!vm->kjit_ready) {
-    const ProgTab t = prog_tab(vm);
-    bool cy = false, ge = false;
-    const char* jerr = "";
-    vm->kjit_fn = xe_jit_get(t.p.data(), t.n.data(), uint32_t(vm->programs.size() - 1), vm->entry, vm->settings.device,
-                             vm->dm_uploaded.data(), uint32_t(vm->dm_uploaded.size() - 1), &cy, &ge, &jerr, 1, nullptr);
-    vm->kjit_ready = true;
-  }
-  return vm->kjit_fn;
-#else
-  (void)vm; (void)jit;
-  return nullptr;
-#endif
-}
-
-// The scalar replay variant of the selected per-program kernel (xe_jit.cpp XE_JV_SEQ, xe_interp.h
-// XE_UNIFORM) for in-order replays of at least kSeqScalarMin packets (a shorter replay costs less than
-// the variant's compile); null when the program has none (the general lane model).
+// A variant of the selected per-program kernel (xe_jit.cpp), built once per kernel on first use:
+// * kKeyedVariant: keyed ordered execution; null when the interpreter runs the keyed passes or the
+//   variant cannot be built. Asked for ahead of the batch that first needs it (xe_prepare, or the start
+//   of a run whose program may write map entries), so no batch's device time includes a compile.
+// * kLeanVariant: verdict-only (XE_JV_LEAN), for parallel runs that ask for no result / register
+//   records; the plain kernel when it cannot be built.
+// * kSeqVariant: the scalar one-lane replay (XE_JV_SEQ, xe_interp.h XE_UNIFORM) for in-order replays of
+//   at least kSeqScalarMin packets (a shorter replay costs less than the variant's compile); null when
+//   the program has none (the general lane model).
+constexpr int kKeyedVariant = 1, kLeanVariant = 2, kSeqVariant = 3;
 constexpr uint32_t kSeqScalarMin = 16384;
-void* seq_kernel(xe_vm* vm, void* jit) {
+void* variant_kernel(xe_vm* vm, void* jit, int variant) {
+  void* fn = nullptr;
 #ifndef XE_HOSTSIM
   if (!jit) return nullptr;
-  if (!vm->sjit_ready) {
+  xe_vm::Variant& v = vm->jit_variants[size_t(variant)];
+  if (!v.ready) {
     const ProgTab t = prog_tab(vm);
     bool cy = false, ge = false;
     const char* jerr = "";
-    vm->sjit_fn = xe_jit_get(t.p.data(), t.n.data(), uint32_t(vm->programs.size() - 1), vm->entry, vm->settings.device,
-                             vm->dm_uploaded.data(), uint32_t(vm->dm_uploaded.size() - 1), &cy, &ge, &jerr, 3, nullptr);
-    vm->sjit_ready = true;
+    v.fn = xe_jit_get(t.p.data(), t.n.data(), uint32_t(vm->programs.size() - 1), vm->entry, vm->settings.device,
+                      vm->dm_uploaded.data(), uint32_t(vm->dm_uploaded.size() - 1), &cy, &ge, &jerr, variant, nullptr);
+    v.ready = true;
   }
-  return vm->sjit_fn;
+  fn = v.fn;
 #else
   (void)vm;
-  (void)jit;
-  return nullptr;
 #endif
-}
-
-// The verdict-only variant of the selected per-program kernel (xe_jit.cpp XE_JV_LEAN) for parallel runs
-// that ask for no result / register records; the plain kernel when it cannot be built.
-void* lean_kernel(xe_vm* vm, void* jit) {
-#ifndef XE_HOSTSIM
-  if (!jit) return nullptr;
-  if (!vm->ljit_ready) {
-    const ProgTab t = prog_tab(vm);
-    bool cy = false, ge = false;
-    const char* jerr = "";
-    vm->ljit_fn = xe_jit_get(t.p.data(), t.n.data(), uint32_t(vm->programs.size() - 1), vm->entry, vm->settings.device,
-                             vm->dm_uploaded.data(), uint32_t(vm->dm_uploaded.size() - 1), &cy, &ge, &jerr, 2, nullptr);
-    vm->ljit_ready = true;
-  }
-  return vm->ljit_fn ? vm->ljit_fn : jit;
-#else
-  (void)vm;
-  return jit;
-#endif
+  return fn || variant != kLeanVariant ? fn : jit;
 }
 
 bool keyed_candidate(const xe_vm* vm) {
@@ -2675,28 +2610,161 @@ static int run_segments(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* 
   return XE_OK;
 }
 
-int xe_run_batch_device(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* d_desc, uint32_t n,
-                        void* d_results, void* d_verdicts, void* d_regs, void* stream, xe_batch_stats* stats) {
-  if (!vm) return XE_ERR_INVAL;
+namespace {
+
+// a batch's statistics from its reduced records
+void publish_stats(xe_batch_stats* st, const std::vector<unsigned long long>& red, uint32_t packets, uint32_t mode_used,
+                   bool conflict, float kernel_ms, uint32_t engine, uint32_t grid) {
+  if (!st) return;
+  st->packets = packets;
+  st->steps = red[1];
+  for (int k = 0; k < 8; k++) st->status_count[k] = red[2 + k];
+  st->mode_used = mode_used;
+  st->conflict = conflict ? 1 : 0;
+  st->kernel_ms = kernel_ms;
+  st->total_ms = kernel_ms;
+  st->engine_used = engine;
+  st->grid_blocks = grid;
+}
+
+// bytes of a HASH map's device slot records (cap slots + the nil key's)
+uint64_t hash_record_bytes(const HostMap& m) { return uint64_t(m.cap + 1) * xe_hash_rwords(m.kwords) * 8; }
+
+// The ordered maps' rollback point of a keyed or in-order run: an LRU map's device snapshot, the others'
+// host mirror (brought up to date here).
+int ordered_rollback_point(xe_vm* vm, xe_stream_t s) {
+  for (size_t i = 1; i < vm->maps.size(); i++) {
+    HostMap& m = vm->maps[i];
+    if (m.dkind == XE_DM_LRU) {  // on the device (the replay keeps its own order log)
+      if (lru_dev_snapshot(m, s)) return fail(vm, XE_ERR_DEVICE, "LRU snapshot");
+    } else if (m.ordered() && map_download(vm, m)) {
+      return fail(vm, XE_ERR_DEVICE, "map download");
+    }
+  }
+  return XE_OK;
+}
+
+// what a keyed attempt came to: the batch is done; it takes the one-lane replay instead (maps, packets
+// and records rolled back); the attempt starts over (a table or pool was grown); or an error (BatchRun::err)
+enum class KeyedResult { Done, Replay, Retry, Error };
+
+// One synchronous batch (xe_run_batch_device): what the run was given, what it chose, the host copies of
+// the device records, and the outcome it publishes. The steps below are its member functions; each leaves
+// the device and the VM as its comment says, and returns XE_OK or the error it recorded (fail).
+struct BatchRun {
+  xe_vm* const vm;
+  void* const d_umem;
+  const uint64_t umem_len;
+  const void* const d_desc;
+  const uint32_t n;
+  void* const d_results;
+  void* const d_verdicts;
+  void* const d_regs;
+  void* const stream;  // as the caller gave it (null: the VM's)
+  xe_batch_stats* const stats;
+  const std::chrono::steady_clock::time_point tm0 = std::chrono::steady_clock::now();
+
+  // prepare()
+  xe_stream_t s = nullptr;
+  XeParams P{};
+  size_t aux_used = 0;
+  uint32_t mode = 0;     // the VM's XE_MODE_* setting
+  void* jit = nullptr;   // the per-program kernel (null: the interpreter)
+  bool jit_general = false;
+  bool general = false;  // lanes keep their state in the XeGen arena
+  bool hostcalls = false, keep_pkts = false, overlap = false, ordmaps = false;
+  bool keyed_ok = false;  // the batch may take the keyed path (set by the driver)
+  std::vector<unsigned long long> aux, red;  // the statistics / footprint records, and their reduction
+  // the ordered maps' header words at the start of the parallel passes / of a keyed attempt
+  std::vector<uint64_t> ord_h0, kh0;
+
+  // outcome
+  uint32_t used = XE_MODE_PARALLEL;
+  bool conflict = false;
+  uint32_t flags = 0;
+  float kms = 0;
+  int err = XE_OK;  // of a keyed attempt that ended in KeyedResult::Error
+
+  // the parallel passes (parallel())
+  void* pj = nullptr;  // their kernel
+  bool lists = false, pops = false, list_conflict = false;
+  uint64_t popped = 0;   // the lists the batch's pops were ranked on (bit m)
+  uint32_t seg_cut = 0;  // > 0: the batch may run as packet-order segments cut there
+  XeListRun lr{};
+
+  // one keyed attempt (keyed())
+  void* kjit = nullptr;  // the per-program kernel's keyed variant
+  uint32_t dmax = 0, dcap = 0, kgrid = 0;
+  XeKeyed K{};
+  XeParams X{};
+  std::vector<uint32_t> small;
+  std::map<size_t, uint64_t> evict;  // LRU map -> the evictions its inserts make
+
   // (tuning build: XE_HOST_TIMING=1 prints host-side marks of the batch, milliseconds since its start)
-  const auto tm0 = std::chrono::steady_clock::now();
-  auto tmark = [&](const char* what) {
+  void tmark(const char* what) const {
     if (xe_tuning_env("XE_HOST_TIMING"))
       fprintf(stderr, "host %-14s %8.3f ms (n=%u)\n", what,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), n);
-  };
+  }
+  // (tuning build: XE_KEYED_TRACE=1 names why a keyed attempt gave up or started over)
+  void keyed_trace(const char* why) const {
+    if (xe_tuning_env("XE_KEYED_TRACE")) fprintf(stderr, "keyed: %s (n=%u)\n", why, n);
+  }
+
+  int prepare();
+  int read_aux();
+  int rollback(bool hash_records);
+  int snap_records();
+  int fold();
+  int sequential();
+  int replay_in_order() { used = XE_MODE_SEQUENTIAL; return sequential(); }
+
+  KeyedResult kfail(int rc, const char* msg) { err = fail(vm, rc, msg); return KeyedResult::Error; }
+  KeyedResult kerror() { err = -1; return KeyedResult::Error; }  // a failed rollback: -1, no message (as before the enum)
+  KeyedResult kreplay(const char* why, bool hash_records = false);
+  int krollback();
+  int kstep(uint32_t st, uint32_t items) { return launch_keyed(&K, vm->d_maps, vm->d_skip, st, items, s); }
+  int read_small() { return d2h(small.data(), vm->d_ksmall, XE_KS_WORDS * 4, s) || dsync(s); }
+  KeyedResult keyed_spec(bool& finished);
+  KeyedResult keyed_build();
+  KeyedResult keyed_capacity();
+  KeyedResult keyed_evictions();
+  KeyedResult keyed_order();
+  KeyedResult keyed_reserve();
+  KeyedResult keyed_remainder();
+  KeyedResult keyed_chains();
+  KeyedResult keyed();
+  KeyedResult keyed_with_retries();
+  int keyed_first();
+
+  int list_setup();
+  int list_init();
+  int list_read() { return d2h(&lr, vm->d_listrun, sizeof lr, s) || dsync(s); }
+  int pass();
+  int ranked_passes();
+  int list_sensitivity();
+  int parallel();
+  int after_conflict();
+  int results_stand();
+  int publish();
+};
+
+// Everything before the first emulator launch: the maps and programs on the device, the launch
+// parameters, this run's LRU epoch, the kernel, the prologue (map value snapshots, zeroed records), the
+// packet snapshot and the descriptor overlap check.
+int BatchRun::prepare() {
   vm->staged_slot = -1;  // this run writes the maps outside the pipeline
   for (size_t i = 1; i < vm->maps.size(); i++) vm->maps[i].dsnap = false;  // rollback points are per run
   if (stats) memset(stats, 0, sizeof *stats);
   if (int rc = xe_sync(vm)) return rc;  // pipelined batches first: they precede this one
-  xe_stream_t s = stream ? (xe_stream_t)stream : vm->stream;
+  s = stream ? (xe_stream_t)stream : vm->stream;
   if (int rc = prepare_run(vm, s)) return rc;
   tmark("prepare_run");
   if (n && (!d_umem || !d_desc)) return fail(vm, XE_ERR_INVAL, "null umem/desc");
   vm->delta_base = true;
 
-  XeParams P = batch_params(vm, d_umem, umem_len, d_desc, n, d_results, d_verdicts, d_regs, vm->d_aux);
-  const size_t aux_used = 16 + size_t(kRep) * P.rep_words;
+  P = batch_params(vm, d_umem, umem_len, d_desc, n, d_results, d_verdicts, d_regs, vm->d_aux);
+  aux_used = 16 + size_t(kRep) * P.rep_words;
   // LRU stamps of this run sort after every earlier run's (xe_interp.h lru_stamp; header word 5)
   {
     bool lru = false;
@@ -2709,16 +2777,11 @@ int xe_run_batch_device(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* 
   }
   if (P.trace && dmemset(vm->d_trace_cnt, 0, vm->trace_pk.size() * 4, s)) return fail(vm, XE_ERR_DEVICE, "trace reset");
   // host functions are called in packet order only
-  const bool hostcalls = calls_host_helper(vm);
+  hostcalls = calls_host_helper(vm);
 
-  const uint32_t mode = vm->settings.mode;
-  void* jit = nullptr;
-  bool jit_general = false;
+  mode = vm->settings.mode;
   if (int rc = select_engine(vm, jit, jit_general)) return rc;
-  const bool general = !jit || jit_general;  // lanes keep their state in the XeGen arena
-  auto launch = [&](const XeParams* p, uint32_t b, uint32_t t) {
-    return jit ? launch_jit(jit, p, b, t, s) : launch_interp(p, b, t, s);
-  };
+  general = !jit || jit_general;
   // one prologue launch: snapshot the map values (rollback point for the ordered fallback and base of
   // the shard deltas) and zero the statistics words
   {
@@ -2736,12 +2799,11 @@ int xe_run_batch_device(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* 
       return fail(vm, XE_ERR_DEVICE, "prologue");
   }
   // the ordered replay must also start from the original packet bytes
-  const bool keep_pkts = mode == XE_MODE_AUTO && umem_len && may_write_packet(vm->programs[vm->entry]);
+  keep_pkts = mode == XE_MODE_AUTO && umem_len && may_write_packet(vm->programs[vm->entry]);
   if (keep_pkts && (ensure_buf(&vm->d_usnap, &vm->d_usnap_cap, umem_len) || d2d(vm->d_usnap, d_umem, umem_len, s)))
     return fail(vm, XE_ERR_DEVICE, "packet snapshot");
   // A packet-writing program over descriptors whose bytes overlap: in the reference's order a later
   // packet reads what an earlier one wrote, which parallel lanes cannot reproduce; in order straight away.
-  bool overlap = false;
   if (keep_pkts && n > 1) {
     size_t need = 0;
     uint32_t flag = 0;
@@ -2753,663 +2815,723 @@ int xe_run_batch_device(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* 
       return fail(vm, XE_ERR_DEVICE, "descriptor overlap check");
     overlap = flag != 0;
   }
-  std::vector<unsigned long long> aux(aux_used);
-  std::vector<unsigned long long> red;
-  // sum / OR the per-wave replicas: [0] flags, replica r at 16 + r * rep_words
-  auto reduce = [&]() { reduce_aux(aux.data(), P.nmaps, P.rep_words, red); };
-  auto read_aux = [&]() -> int {
-    if (d2h(aux.data(), vm->d_aux, aux_used * 8, s) || dsync(s)) return -1;
-    reduce();
-    return 0;
-  };
-  // roll maps and packets back to the run's start
-  auto rollback = [&](bool hash_records) -> int {
-    for (size_t i = 1; i < vm->maps.size(); i++) {
-      HostMap& m = vm->maps[i];
-      if (!m.ordered() && d2d(m.d_vals, m.d_snap, m.vals_alloc, s)) return -1;
-    }
-    if (hash_records) {
-      uint64_t off = 0;
-      for (size_t i = 1; i < vm->maps.size(); i++) {
-        HostMap& m = vm->maps[i];
-        if (m.dkind != XE_DM_HASH) continue;
-        const uint64_t rb = uint64_t(m.cap + 1) * xe_hash_rwords(m.kwords) * 8;
-        if (d2d(m.d_keys, (uint8_t*)vm->d_ksnap + off, rb, s) || d2d(m.d_count, (uint8_t*)vm->d_ksnap + off + rb, 4, s)) return -1;
-        off += rb + 8;
-      }
-      for (size_t i = 1; i < vm->maps.size(); i++) {  // the ordered maps come back from their rollback point:
-        HostMap& m = vm->maps[i];                       // an LRU map's device snapshot, the others' host mirror
-        if (m.dkind == XE_DM_LRU && m.dsnap) {
-          if (lru_dev_restore(m, s)) return -1;
-        } else if (m.ordered() && ordered_upload(vm, m, vm->ord_slack, vm->ord_slack_bytes)) {
-          return -1;
-        }
-      }
-    }
-    if (keep_pkts && d2d(d_umem, vm->d_usnap, umem_len, s)) return -1;
-    return dmemset(vm->d_aux, 0, aux_used * 8, s);
-  };
-  // The exact ordered replay: one lane walks the packets in order. Its arena (and the ordered maps'
-  // room) grows x4 and the replay restarts from the rollback point whenever it runs out.
-  // rollback point of what the parallel pass never writes: hash slot records (+ counts)
-  auto snap_records = [&]() -> int {
-    uint64_t kb = 0;
-    for (size_t i = 1; i < vm->maps.size(); i++)
-      if (vm->maps[i].dkind == XE_DM_HASH) kb += uint64_t(vm->maps[i].cap + 1) * xe_hash_rwords(vm->maps[i].kwords) * 8 + 8;
-    if (kb && ensure_buf((void**)&vm->d_ksnap, &vm->d_ksnap_bytes, kb)) return fail(vm, XE_ERR_DEVICE, "device alloc (snapshot)");
-    uint64_t off = 0;
-    for (size_t i = 1; i < vm->maps.size(); i++) {
-      HostMap& m = vm->maps[i];
-      if (m.dkind != XE_DM_HASH) continue;
-      const uint64_t rb = uint64_t(m.cap + 1) * xe_hash_rwords(m.kwords) * 8;
-      if (d2d((uint8_t*)vm->d_ksnap + off, m.d_keys, rb, s) || d2d((uint8_t*)vm->d_ksnap + off + rb, m.d_count, 4, s))
-        return fail(vm, XE_ERR_DEVICE, "snapshot");
-      off += rb + 8;
-    }
-    return XE_OK;
-  };
-  auto sequential = [&](float& ms) -> int {
-    // rollback point of what the parallel pass never writes: hash slot records, the ordered maps
-    if (int rc = snap_records()) return rc;
-    for (size_t i = 1; i < vm->maps.size(); i++) {
-      HostMap& m = vm->maps[i];
-      if (m.dkind == XE_DM_LRU) {  // rollback point on the device (the replay keeps its own order log)
-        if (lru_dev_snapshot(m, s)) return fail(vm, XE_ERR_DEVICE, "LRU snapshot");
-      } else if (m.ordered() && map_download(vm, m)) {
-        return fail(vm, XE_ERR_DEVICE, "map download");
-      }
-    }
-    // the replay lane's packets are staged 64 at a time by the whole wave unless a packet may write
-    // packet bytes a later packet reads (its window must then be fetched after the earlier writes)
-    P.seq_prefetch = may_write_packet(vm->programs[vm->entry]) ? 0u : 1u;
-    // and run ahead of the lane (per-program kernels; XE_SEQ_PEEK=0 in the tuning build: A/B)
-    if (P.seq_prefetch) {
-      const char* pk = xe_tuning_env("XE_SEQ_PEEK");
-      if (!pk || atoi(pk)) P.seq_prefetch |= 2u;
-    }
-    for (int attempt = 0;; attempt++) {
-      P.mode = XE_MODE_SEQUENTIAL;
-      if (general && ensure_arena(vm, true, 1, P.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (replay arena)");
-      bool table = false;  // the LRU maps' order logs from their stamps (the run's start state)
-      for (size_t i = 1; i < vm->maps.size(); i++) {
-        if (vm->maps[i].dkind != XE_DM_LRU) continue;
-        const int r = lru_log_build(vm, vm->maps[i], s);
-        if (r < 0) return fail(vm, XE_ERR_DEVICE, "LRU order log");
-        table = table || r > 0;
-      }
-      if (table) {
-        if (int rc = upload_map_table(vm, s)) return rc;
-        P.maps = vm->d_maps;
-      }
-      vm->t1.rec(s);
-      // a long replay on the scalar variant of the per-program kernel (every lane runs the packet)
-      void* sj = (jit && !jit_general && n >= kSeqScalarMin) ? seq_kernel(vm, jit) : nullptr;
-      if (sj ? launch_jit(sj, &P, 1, 64, s) : launch(&P, 1, 64)) return fail(vm, XE_ERR_DEVICE, "kernel launch");
-      vm->t2.rec(s);
-      if (hostcalls && serve_hostcalls(vm->h_hostcall, s)) return fail(vm, XE_ERR_DEVICE, "kernel failed (host helpers)");
-      if (read_aux()) return fail(vm, XE_ERR_DEVICE, "kernel failed");
-      ms += Timer::ms(vm->t1, vm->t2);
-      if (!(red[0] & XE_FLAG_CAPACITY)) {
-        for (size_t i = 1; i < vm->maps.size(); i++)  // the replay kept stamps and its log, not the links
-          if (vm->maps[i].dkind == XE_DM_LRU) vm->maps[i].links_stale = true;
-        return XE_OK;
-      }
-      if (attempt >= 6) return fail(vm, XE_ERR_NOMEM, "the ordered replay outgrew its device arena");
-      vm->seq_scale *= 4;
-      vm->ord_slack *= 4;
-      vm->ord_slack_bytes *= 4;
-      if (rollback(true)) return fail(vm, XE_ERR_DEVICE, "rollback");
-      // the ordered maps' room grows with the slack: an LRU map, back at its start state on the device,
-      // goes through the host mirror into a larger pool, and that becomes the next attempt's rollback point
-      for (size_t i = 1; i < vm->maps.size(); i++) {
-        HostMap& m = vm->maps[i];
-        if (m.dkind != XE_DM_LRU) continue;
-        m.dev_dirty = true;
-        if (map_download(vm, m)) return fail(vm, XE_ERR_DEVICE, "map download");
-        m.host_dirty = true;
-      }
-      if (prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
-      for (size_t i = 1; i < vm->maps.size(); i++)
-        if (vm->maps[i].dkind == XE_DM_LRU && lru_dev_snapshot(vm->maps[i], s)) return fail(vm, XE_ERR_DEVICE, "LRU snapshot");
-      P.maps = vm->d_maps;
-    }
-  };
-
-  // fold the 8-byte-add replicas into the value regions (and zero them for the next run)
-  auto fold = [&]() -> int {
-    for (size_t i = 1; i < vm->maps.size(); i++) {
-      HostMap& m = vm->maps[i];
-      if (m.nrep > 1 && fold_map(m, s)) return -1;
-      if (m.dkind == XE_DM_LRU && m.trep_r > 1 && launch_lru_tag_fold(m.d_tag, m.d_trep, m.pool_cap, m.trep_r, m.d_hdr, s)) return -1;
-    }
-    return 0;
-  };
-  const bool ordmaps = has_ordered_maps(vm);
-  // Keyed ordered execution (xe_internal.h): the SPEC pass, the build, the parallel pass of the packets
-  // on no chain, the chains. Returns 1 when the batch has to take the one-lane replay instead (maps,
-  // packets and records rolled back), 0 when done (used: XE_MODE_PARALLEL when no packet wrote a map
-  // entry, so the SPEC pass was an ordinary parallel run; else XE_MODE_KEYED), < 0 on error.
-  // (tuning build: XE_KEYED_TRACE=1 names why a keyed attempt gave up or started over)
-  auto keyed_trace = [&](const char* why) {
-    if (xe_tuning_env("XE_KEYED_TRACE")) fprintf(stderr, "keyed: %s (n=%u)\n", why, n);
-  };
-  auto keyed = [&](uint32_t& used_out) -> int {
-    void* kjit = keyed_kernel(vm, jit);  // the per-program kernel's keyed variant
-    if (jit && !kjit) return 1;
-    auto klaunch = [&](const XeParams* p, uint32_t b) { return kjit ? launch_jit(kjit, p, b, 256, s) : launch_interp(p, b, 256, s); };
-    // D table: 4x the last keyed batch's D keys (first time: n / 4), at most 2n (D holds <= n keys)
-    uint32_t dmax = 4096, dcap = 4096;
-    while (dmax < 2ull * n && dmax < (1u << 30)) dmax <<= 1;
-    const uint64_t dwant = vm->keyed_dnext ? vm->keyed_dnext : std::max<uint64_t>(4096, n / 4);
-    while (dcap < dwant && dcap < dmax) dcap <<= 1;
-    tmark("keyed start");
-    if (keyed_alloc(vm, n, dcap)) return fail(vm, XE_ERR_NOMEM, "device alloc (keyed execution)");
-    tmark("keyed alloc");
-    // ordered maps (LRU_HASH keys, appends): the host mirror holds the batch's start (rollback(true)
-    // rebuilds the device copies from it), kh0 their header words / LRU value pools for the cheaper
-    // rollbacks before any record was claimed
-    std::vector<uint64_t> kh0;
-    if (ordmaps) {
-      for (size_t i = 1; i < vm->maps.size(); i++) {
-        HostMap& m = vm->maps[i];
-        if (m.dkind == XE_DM_LRU) {
-          if (lru_dev_snapshot(m, s)) return fail(vm, XE_ERR_DEVICE, "LRU snapshot");
-        } else if (m.ordered() && map_download(vm, m)) {
-          return fail(vm, XE_ERR_DEVICE, "map download");
-        }
-      }
-      tmark("map snapshot");
-      if (ordered_hdr_read(vm, kh0, s)) return fail(vm, XE_ERR_DEVICE, "ordered map header");
-      tmark("hdr read");
-    }
-    auto krollback = [&]() -> int {
-      if (rollback(false)) return -1;
-      return ordmaps ? ordered_hdr_restore(vm, kh0, s) : 0;
-    };
-    XeKeyed K = vm->kd;
-    K.n = n;
-    if (dmemset(K.dkid, 0, uint64_t(K.dcap) * 8, s) || dmemset(vm->d_ksmall, 0, XE_KS_WORDS * 4, s) ||
-        dmemset(K.dfirst, 0xff, uint64_t(K.dcap) * 4, s) || dmemset(K.dvict, 0xff, uint64_t(K.dcap) * 4, s))
-      return fail(vm, XE_ERR_DEVICE, "keyed reset");
-    const uint32_t grid = parallel_grid(vm, kjit, general, n, P.nmaps);
-    XeParams X = P;
-    if (general && ensure_arena(vm, false, grid * 256, X.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (arena)");
-    tmark("arena");
-    // 1. SPEC: every packet against the start state, writes held back, keys logged
-    X.mode = XE_MODE_SPEC;
-    X.K = K;
-    if (klaunch(&X, grid) || fold()) return fail(vm, XE_ERR_DEVICE, "kernel launch (keyed spec)");
-    if (read_aux()) return fail(vm, XE_ERR_DEVICE, "kernel failed (keyed spec)");
-    uint32_t flags = uint32_t(red[0]);
-    if (ordmaps && (flags & XE_FLAG_CAPACITY) && !(flags & XE_FLAG_ORDERED)) {
-      // appends past an ordered map's device room (the parallel branch's ordered_grow): the room
-      // grows to what the pass tried to append and the keyed path starts over
-      const int g = ordered_grow(vm, kh0, s);
-      if (g < 0) return fail(vm, XE_ERR_DEVICE, "ordered map room");
-      if (g == 1) {
-        if (rollback(false) || prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
-        P.maps = vm->d_maps;
-        keyed_trace("spec capacity: grown");
-        return 2;
-      }
-    }
-    if (flags & (XE_FLAG_ORDERED | XE_FLAG_CAPACITY)) { keyed_trace("spec ordered/capacity"); return krollback() ? -1 : 1; }
-    if (!(flags & XE_FLAG_KEYED)) {  // no packet wrote a map entry: an ordinary parallel run
-      if (run_conflict(red, P.nmaps)) { keyed_trace("spec conflict"); return krollback() ? -1 : 1; }
-      if (ordmaps && ordered_finalize(vm, kh0, n, s)) return fail(vm, XE_ERR_DEVICE, "ordered map appends");
-      used_out = XE_MODE_PARALLEL;
-      return 0;
-    }
-    // 2. build: D, chains (union-find rounds), each packet's chain, the sorted order
-    auto step = [&](uint32_t st, uint32_t items) { return launch_keyed(&K, vm->d_maps, vm->d_skip, st, items, s); };
-    std::vector<uint32_t> small(XE_KS_WORDS);
-    auto read_small = [&]() { return d2h(small.data(), vm->d_ksmall, XE_KS_WORDS * 4, s) || dsync(s); };
-    if (step(XE_KS_DSET, n)) return fail(vm, XE_ERR_DEVICE, "keyed build");
-    for (int round = 0;; round++) {
-      if (round >= 64) { keyed_trace("union rounds"); return krollback() ? -1 : 1; }
-      if (dmemset(K.changed, 0, 4, s) || step(XE_KS_UNION, n) || read_small()) return fail(vm, XE_ERR_DEVICE, "keyed build");
-      if (!small[XE_KS_CHANGED]) break;
-    }
-    if (step(XE_KS_COMPRESS, K.dcap) || step(XE_KS_ASSIGN, n) || step(XE_KS_COUNT, K.dcap) || read_small())
-      return fail(vm, XE_ERR_DEVICE, "keyed build");
-    if (small[XE_KS_ERR] & 8u) {  // D outgrew its table: once more with room for every packet's key
-      vm->keyed_dnext = dmax;
-      if (dcap < dmax) { keyed_trace("D full"); return krollback() ? -1 : 2; }
-    }
-    // key log overflow (1), a root walk that did not end (16): the in-order replay
-    if (small[XE_KS_ERR]) { keyed_trace(small[XE_KS_ERR] & 16u ? "root walk" : "key log overflow"); return krollback() ? -1 : 1; }
-    {
-      uint64_t nd = 0;
-      for (uint32_t i = 0; i < 64; i++) nd += small[XE_KS_DCOUNT + i];
-      uint64_t next = 4096;
-      while (next < 4 * nd && next < dmax) next <<= 1;
-      vm->keyed_dnext = uint32_t(next);
-    }
-    std::map<size_t, uint64_t> evict;  // LRU map -> the evictions its inserts make
-    // a HASH insert can fail for capacity only in an order-dependent way (and an LRU insert would evict
-    // by the batch's order of touches): every key some packet inserts fits. Only an absent key's insert
-    // meets the capacity rule (maps_hash.go:84-89, maps_hash_lru.go:114-119) and nothing deletes in a
-    // keyed batch, so the bound is the live count + the D keys a packet inserts (XE_KS_DINS); keys
-    // that are only looked up, promoted or updated in place do not count
-    for (size_t i = 1; i < vm->maps.size() && i < 64; i++) {
-      HostMap& m = vm->maps[i];
-      const uint64_t nd = small[XE_KS_DINS + i];
-      if ((m.dkind != XE_DM_HASH && m.dkind != XE_DM_LRU) || !nd) continue;
-      uint64_t cnt = 0;
-      if (m.dkind == XE_DM_HASH) {
-        uint32_t c32 = 0;
-        if (d2h(&c32, m.d_count, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "count");
-        cnt = c32;
-      } else {
-        cnt = kh0[i * 8 + 2];
-        // value ids for every new key that does not take over its victim's (keyed_lruid_item): grow the
-        // pool and run again
-        const uint64_t ev = cnt + nd > m.def.max_entries ? cnt + nd - m.def.max_entries : 0;
-        if (kh0[i * 8 + 3] + (nd - ev) > m.pool_cap) {
-          if (krollback() || map_download(vm, m)) return -1;  // the mirror: the batch's start
-          vm->ord_slack = std::max<uint64_t>(vm->ord_slack, 2 * nd + 4096);
-          m.host_dirty = true;  // rebuilt from the mirror with the larger pool
-          if (prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "ordered map room");
-          P.maps = vm->d_maps;
-          keyed_trace("LRU pool grown");
-          return 2;
-        }
-      }
-      if (cnt + nd > m.def.max_entries) {
-        if (m.dkind != XE_DM_LRU) { keyed_trace("capacity"); return krollback() ? -1 : 1; }
-        evict[i] = cnt + nd - m.def.max_entries;  // the batch's inserts evict: planned below
-      }
-    }
-    // LRU evictions (xe_interp.h keyed_evict_item): rank every LRU map's new keys by their first
-    // inserting packet, give the inserts past the map's room the oldest values of the batch's start as
-    // victims, and replay in order if any packet of the batch touches one of them
-    if (!evict.empty()) {
-      size_t eb = 0;
-      if (step(XE_KS_FIRST, n) || step(XE_KS_EKEY, K.dcap) || launch_keyed_esort(&K, nullptr, &eb, s) ||
-          ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, eb) || launch_keyed_esort(&K, vm->d_ksort, &eb, s))
-        return fail(vm, XE_ERR_DEVICE, "keyed evictions");
-      uint64_t off = 0;
-      for (size_t i = 1; i < vm->maps.size() && i < 64; i++) {
-        HostMap& m = vm->maps[i];
-        if (m.dkind != XE_DM_LRU) continue;
-        const uint32_t nd = small[XE_KS_DINS + i];
-        if (evict.count(i)) {
-          const uint64_t cnt = kh0[i * 8 + 2];
-          // the start's UsageList by stamp (the stamps at the batch's start: the snapshot of ordered_hdr_read)
-          size_t rb = 0;
-          if (launch_lru_relink(m.d_tsnap, m.pool_cap, uint32_t(cnt), m.d_link, m.d_hdr, nullptr, &rb, 2, s) ||
-              ensure_buf(&vm->d_relink, &vm->d_relink_cap, rb) ||
-              launch_lru_relink(m.d_tsnap, m.pool_cap, uint32_t(cnt), m.d_link, m.d_hdr, vm->d_relink, &rb, 2, s))
-            return fail(vm, XE_ERR_DEVICE, "keyed evictions (order)");
-          K.em = uint32_t(i);
-          K.eoff = uint32_t(off);
-          K.efree = uint32_t(m.def.max_entries - cnt);
-          K.ecnt0 = uint32_t(cnt);
-          K.etsnap = m.d_tsnap;
-          K.vorder = lru_sorted_ids(vm->d_relink, m.pool_cap);
-          if (step(XE_KS_EVICT, nd) || step(XE_KS_EMARK, nd)) return fail(vm, XE_ERR_DEVICE, "keyed evictions");
-        }
-        off += nd;
-      }
-      if (read_small()) return fail(vm, XE_ERR_DEVICE, "keyed evictions");
-      if (small[XE_KS_ERR] & 8u) {  // the victims' keys did not fit the D table
-        vm->keyed_dnext = dmax;
-        if (dcap < dmax) { keyed_trace("D full (victims)"); return krollback() ? -1 : 2; }
-      }
-      if (small[XE_KS_ERR]) { keyed_trace("eviction seen by the batch"); return krollback() ? -1 : 1; }
-      K.em = 0;
-    }
-    uint32_t end_bit = 1;
-    while ((1ull << end_bit) <= K.dcap) end_bit++;
-    size_t sb = 0;
-    if (step(XE_KS_IOTA, n) || launch_keyed_sort(&K, n, end_bit, nullptr, &sb, s) ||
-        ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, sb) || launch_keyed_sort(&K, n, end_bit, vm->d_ksort, &sb, s))
-      return fail(vm, XE_ERR_DEVICE, "keyed sort");
-    if (step(XE_KS_NCHAIN, n) || read_small()) return fail(vm, XE_ERR_DEVICE, "keyed build");
-    K.nO = small[XE_KS_NO];
-    // one chain with more than half the packets (a hot key written by most of them): its lane would
-    // take longer than the staged one-lane replay of the whole batch
-    if (step(XE_KS_CSTART, K.nO) || step(XE_KS_CLONG, K.nO) || read_small()) return fail(vm, XE_ERR_DEVICE, "keyed build");
-    if (small[XE_KS_LONG]) { keyed_trace("long chain"); return krollback() ? -1 : 1; }
-    // 3. back to the start state; reserve a slot record for every new HASH key of D
-    if (krollback() || snap_records()) return fail(vm, XE_ERR_DEVICE, "rollback");
-    if (ordmaps && step(XE_KS_LRUID, K.dcap)) return fail(vm, XE_ERR_DEVICE, "keyed value ids");
-    if (step(XE_KS_RESERVE, K.dcap) || read_small()) return fail(vm, XE_ERR_DEVICE, "keyed reserve");
-    if (small[XE_KS_ERR]) { keyed_trace("reserve"); return rollback(true) ? -1 : 1; }
-    // 4. the packets on no chain, in parallel (the fast kernel: the skip mask is its only keyed input)
-    X.mode = XE_MODE_PARALLEL;
-    X.K = K;
-    X.K.skip = vm->d_skip;
-    if (K.nO < n) {
-      XeParams Y = X;
-      const uint32_t pgrid = parallel_grid(vm, jit, general, n, P.nmaps);
-      if (general && ensure_arena(vm, false, pgrid * 256, Y.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (arena)");
-      if (launch(&Y, pgrid, 256) || fold()) return fail(vm, XE_ERR_DEVICE, "kernel launch (keyed parallel)");
-    }
-    // 5. the chains in packet order: the compacted chain list is a work queue the waves claim from
-    {
-      size_t sb2 = 0;
-      if (step(XE_KS_CFLAG, K.nO) || launch_keyed_scan(&K, K.nO, nullptr, &sb2, s) ||
-          ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, sb2) || launch_keyed_scan(&K, K.nO, vm->d_ksort, &sb2, s) ||
-          step(XE_KS_CLIST, K.nO) || dmemset(vm->d_ksmall + XE_KS_CNEXT, 0, 4, s))
-        return fail(vm, XE_ERR_DEVICE, "keyed chain list");
-    }
-    X.mode = XE_MODE_CHAIN;
-    X.K.skip = nullptr;
-    const uint32_t cgrid = std::max<uint32_t>(1, std::min<uint32_t>(grid, (K.nO + 255) / 256));
-    if (general && ensure_arena(vm, false, cgrid * 256, X.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (arena)");
-    if (klaunch(&X, cgrid) || step(XE_KS_UNNEW, K.dcap)) return fail(vm, XE_ERR_DEVICE, "kernel launch (keyed chains)");
-    if (read_aux() || read_small()) return fail(vm, XE_ERR_DEVICE, "kernel failed (keyed chains)");
-    if (run_conflict(red, P.nmaps)) { keyed_trace("chain conflict"); return rollback(true) ? -1 : 1; }  // a packet left its chain / an order-dependent add
-    // the chains' inserts into the map counts (LRU_HASH: header word 2, less its evictions). An LRU map
-    // with evictions must have seen every ranked insert: one that did not happen shifts the victims of
-    // the inserts after it
-    for (const auto& [i, ev] : evict) {
-      uint32_t add = 0;
-      for (uint32_t k = 0; k < XE_KSTRIPES; k++) add += small[XE_KS_CINS + i * XE_KSTRIPES + k];
-      if (add != small[XE_KS_DINS + i]) { keyed_trace("eviction ranks"); return rollback(true) ? -1 : 1; }
-    }
-    for (size_t i = 1; i < vm->maps.size() && i < 64; i++) {
-      HostMap& m = vm->maps[i];
-      uint32_t add = 0;
-      for (uint32_t k = 0; k < XE_KSTRIPES; k++) add += small[XE_KS_CINS + i * XE_KSTRIPES + k];
-      if (!add) continue;
-      if (m.dkind == XE_DM_HASH) {
-        uint32_t cnt = 0;
-        if (d2h(&cnt, m.d_count, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "count");
-        cnt += add;
-        if (h2d(m.d_count, &cnt, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "count");
-      } else if (m.dkind == XE_DM_LRU) {
-        uint64_t cnt = 0;
-        if (d2h(&cnt, m.d_hdr + 2, 8, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "count");
-        cnt += add;
-        if (evict.count(i)) cnt -= evict[i];
-        if (h2d(m.d_hdr + 2, &cnt, 8, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "count");
-      }
-    }
-    // the appends and LRU touches of both passes into packet order
-    if (ordmaps && ordered_finalize(vm, kh0, n, s)) return fail(vm, XE_ERR_DEVICE, "ordered map appends");
-    vm->last_grid = grid;
-    used_out = XE_MODE_KEYED;
-    return 0;
-  };
-
-  if (jit && keyed_candidate(vm)) keyed_kernel(vm, jit);  // built before the timed region
+  aux.resize(aux_used);
+  ordmaps = has_ordered_maps(vm);
+  if (jit && keyed_candidate(vm)) variant_kernel(vm, jit, kKeyedVariant);  // built before the timed region
   vm->t0.rec(s);
-  bool conflict = false;
-  uint32_t used = XE_MODE_PARALLEL;
-  float kms = 0;
-  // ordered maps: appends and LRU lookups run in parallel (put in packet order afterwards), LRU updates
-  // through the keyed path; a batch with any other operation on them (pops, peeks, list lookups, an LRU
-  // eviction) replays in order, and so do the next few after such a batch
   tmark("setup");
   if (!vm->keyed_hint_set && n > 0) {
     vm->keyed_hint_set = true;
     if (lru_update_sites(vm)) vm->keyed_hint = true;
   }
-  const bool ord_par = !ordmaps || ordered_parallel_ok(vm);
-  const bool keyed_ok = mode == XE_MODE_AUTO && n > 0 && !overlap && ord_par;
-  bool ord_seq = mode == XE_MODE_AUTO && ordmaps && (!ord_par || vm->ord_backoff);
-  if (ord_seq && vm->ord_backoff) vm->ord_backoff--;
-  std::vector<uint64_t> ord_h0;
-  if (mode == XE_MODE_SEQUENTIAL || ord_seq || overlap || hostcalls) {
-    used = XE_MODE_SEQUENTIAL;
-    if (int rc = sequential(kms)) return rc;
-  } else if (keyed_ok && vm->keyed_hint) {
-    // the last batch wrote map entries: straight to the keyed path
-    int r = keyed(used);
-    for (int t = 0; r == 2 && t < 3; t++) r = keyed(used);  // its D table / an LRU pool was too small
-    if (r == 2) r = 1;
-    if (r < 0) return r;
-    if (r == 1) {
-      vm->keyed_backoff = kKeyedBackoff;
-      if (ordmaps) vm->ord_backoff = kKeyedBackoff;
-      used = XE_MODE_SEQUENTIAL;
-      if (int rc = sequential(kms)) return rc;
+  return XE_OK;
+}
+
+// the records of the launches so far: sum / OR the per-wave replicas ([0] flags, replica r at 16 + r * rep_words)
+int BatchRun::read_aux() {
+  if (d2h(aux.data(), vm->d_aux, aux_used * 8, s) || dsync(s)) return -1;
+  reduce_aux(aux.data(), P.nmaps, P.rep_words, red);
+  return 0;
+}
+
+// Where the HASH maps' slot records and counts sit in the VM's snapshot buffer (d_ksnap): one map after
+// the other, each its records then 8 bytes for its count. Returns the bytes they take together.
+struct HashSnap {
+  HostMap* m;
+  uint64_t off, rb;  // offset of the records, their bytes (the count follows them)
+};
+uint64_t hash_snapshot_layout(xe_vm* vm, std::vector<HashSnap>& out) {
+  uint64_t off = 0;
+  for (size_t i = 1; i < vm->maps.size(); i++) {
+    HostMap& m = vm->maps[i];
+    if (m.dkind != XE_DM_HASH) continue;
+    out.push_back({&m, off, hash_record_bytes(m)});
+    off += out.back().rb + 8;
+  }
+  return off;
+}
+
+// roll maps and packets back to the run's start
+int BatchRun::rollback(bool hash_records) {
+  for (size_t i = 1; i < vm->maps.size(); i++) {
+    HostMap& m = vm->maps[i];
+    if (!m.ordered() && d2d(m.d_vals, m.d_snap, m.vals_alloc, s)) return -1;
+  }
+  if (hash_records) {
+    std::vector<HashSnap> snaps;
+    hash_snapshot_layout(vm, snaps);
+    for (const HashSnap& h : snaps) {
+      uint8_t* at = (uint8_t*)vm->d_ksnap + h.off;
+      if (d2d(h.m->d_keys, at, h.rb, s) || d2d(h.m->d_count, at + h.rb, 4, s)) return -1;
     }
-    conflict = used != XE_MODE_PARALLEL;
-    vm->t1.rec(s);
-    if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "sync");
-    kms += Timer::ms(vm->t0, vm->t1);
-  } else {
-    P.mode = XE_MODE_PARALLEL;
-    void* pj = (jit && !P.results && !P.regs) ? lean_kernel(vm, jit) : jit;  // verdicts only: the lean variant
-    vm->last_grid = parallel_grid(vm, pj, general, n, P.nmaps);
-    if (general && ensure_arena(vm, false, vm->last_grid * 256, P.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (arena)");
-    uint32_t flags = 0;
-    uint32_t seg_cut = 0;  // > 0: the batch may run as packet-order segments cut there
-    // QUEUE / STACK pops, peeks and lookups in parallel (xe_interp.h list_pos): the run's list record,
-    // and for a program that may pop, a count pass first (which packets pop: their prefix sum is each
-    // pop's rank in packet order), then the pass proper from the batch's start again
-    const bool lists = ordmaps && n > 0 && has_list_maps(vm);
-    const bool pops = lists && may_pop(vm);
-    bool list_conflict = false;
-    uint64_t popped = 0;  // the lists the batch's pops were ranked on (bit m)
-    if (lists) {
-      if (!vm->d_listrun && dev_alloc((void**)&vm->d_listrun, sizeof(XeListRun))) return fail(vm, XE_ERR_NOMEM, "device alloc (lists)");
-      P.list = vm->d_listrun;
-      if (pops && vm->pop_n < n) {
-        dev_free(vm->d_popflag); dev_free(vm->d_popbase); dev_free(vm->d_popused);
-        vm->d_popflag = vm->d_popbase = vm->d_popused = nullptr;
-        vm->pop_n = 0;
-        if (dev_alloc((void**)&vm->d_popflag, size_t(n) * 4) || dev_alloc((void**)&vm->d_popbase, size_t(n) * 4 * XE_POP_SLOTS) ||
-            dev_alloc((void**)&vm->d_popused, size_t(n) * 4))
-          return fail(vm, XE_ERR_NOMEM, "device alloc (pop ranks)");
-        vm->pop_n = n;
-      }
-    }
-    XeListRun lr{};
-    auto list_init = [&]() -> int {  // start counts from the headers, no sensitive op, no push yet
-      memset(&lr, 0, sizeof lr);
-      for (size_t i = 1; i < vm->maps.size() && i < 64; i++)
-        if (vm->maps[i].dkind == XE_DM_LIST) lr.cnt0[i] = uint32_t(ord_h0[i * 8 + 1]);
-      for (int i = 0; i < 64; i++) lr.push[i] = lr.senslo[i] = 0xffffffffu;
-      return h2d(vm->d_listrun, &lr, sizeof lr, s);
-    };
-    auto list_read = [&]() -> int { return d2h(&lr, vm->d_listrun, sizeof lr, s) || dsync(s); };
-    auto pass = [&]() -> int {
-      if (pj ? launch_jit(pj, &P, vm->last_grid, 256, s) : launch_interp(&P, vm->last_grid, 256, s))
-        return fail(vm, XE_ERR_DEVICE, "kernel launch");
-      vm->t1.rec(s);  // kernel_ms: the emulator kernel alone
-      if (fold()) return fail(vm, XE_ERR_DEVICE, "replica fold");
-      if (read_aux()) return fail(vm, XE_ERR_DEVICE, "kernel failed");
-      kms = Timer::ms(vm->t0, vm->t1);
-      flags = uint32_t(red[0]);
-      conflict = run_conflict(red, P.nmaps);
-      return XE_OK;
-    };
-    for (int attempt = 0;; attempt++) {
-      if (ordmaps && ordered_hdr_read(vm, ord_h0, s)) return fail(vm, XE_ERR_DEVICE, "ordered map header");
-      if (lists && list_init()) return fail(vm, XE_ERR_DEVICE, "list run");
-      tmark("ordered hdr");
-      if (pops) {
-        P.pop_mode = 1;
-        P.popflag = vm->d_popflag;
-        P.popbase = nullptr;
-        if (dmemset(vm->d_popflag, 0, size_t(n) * 4, s)) return fail(vm, XE_ERR_DEVICE, "pop flags");
-        if (int rc = pass()) return rc;
-        tmark("count pass");
-        if (!conflict) {
-          if (list_read()) return fail(vm, XE_ERR_DEVICE, "list run");
-          // Ranked passes: each popped list gets a slot; a packet's pops of it are counted in 8 bits of its
-          // word (the count pass's first pops, then what the last ranked pass observed), the counts of each
-          // slot are scanned into ranks, and the pass runs again from the batch's start until every packet
-          // made exactly the pops it was ranked by (a pop after a peek, a second pop, or pops from another
-          // list change what the count pass saw). Up to 4 passes; then, or with more than XE_POP_SLOTS
-          // popped lists, the batch replays in order.
-          uint64_t mask = lr.popmask;
-          bool ranked = false;
-          for (int it = 0; it < 4 && !conflict; it++) {
-            if (__builtin_popcountll(mask) > int(XE_POP_SLOTS)) break;
-            XePopSlots sl;
-            memset(sl.slot, 0xff, sizeof sl.slot);
-            uint32_t ns = 0;
-            for (uint32_t m = 0; m < 64; m++)
-              if ((mask >> m) & 1) sl.slot[m] = uint8_t(ns++);
-            memcpy(P.pop_slot, sl.slot, sizeof sl.slot);
-            P.pop_stride = n;
-            // the counts to rank by: packed count-pass flags first, then the last pass's observed counts
-            if (it == 0 ? launch_pop(vm->d_popflag, vm->d_popused, n, 0, 0, sl, nullptr, s)
-                        : d2d(vm->d_popused, vm->d_popflag, size_t(n) * 4, s))
-              return fail(vm, XE_ERR_DEVICE, "pop ranks");
-            for (uint32_t j = 0; j < ns; j++) {
-              XeKeyed S{};
-              S.iota = vm->d_popflag;  // (free until the pass writes its observed counts)
-              S.ckey = vm->d_popbase + size_t(j) * n;
-              size_t sb = 0;
-              if (launch_pop(vm->d_popused, vm->d_popflag, n, 1, j, sl, nullptr, s) ||
-                  launch_keyed_scan(&S, n, nullptr, &sb, s) || ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, sb) ||
-                  launch_keyed_scan(&S, n, vm->d_ksort, &sb, s))
-                return fail(vm, XE_ERR_DEVICE, "pop ranks");
-            }
-            if (rollback(false) || ordered_hdr_restore(vm, ord_h0, s) || list_init()) return fail(vm, XE_ERR_DEVICE, "pop ranks");
-            tmark("ranks");
-            P.pop_mode = 2;
-            P.popbase = vm->d_popbase;
-            if (int rc = pass()) return rc;
-            tmark("ranked pass");
-            if (conflict) break;
-            if (list_read()) return fail(vm, XE_ERR_DEVICE, "list run");
-            if (lr.newlist) {  // a pop of a list with no slot: rank it too
-              mask |= lr.popmask;
-              continue;
-            }
-            if (ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, 256)) return fail(vm, XE_ERR_NOMEM, "pop ranks");
-            uint32_t* d_flag = (uint32_t*)vm->d_ksort;  // (the scans' scratch, free now)
-            uint32_t mismatch = 0;
-            if (dmemset(d_flag, 0, 4, s) || launch_pop(vm->d_popflag, vm->d_popused, n, 2, 0, sl, d_flag, s) ||
-                d2h(&mismatch, d_flag, 4, s) || dsync(s))
-              return fail(vm, XE_ERR_DEVICE, "pop ranks");
-            if (!mismatch) {
-              ranked = true;
-              popped = mask;
-              break;
-            }
-          }
-          if (!ranked && !conflict) {
-            list_conflict = conflict = true;
-            flags |= XE_FLAG_ORDERED;
-          }
-        }
-      } else if (int rc = pass()) {
-        return rc;
-      }
-      if (!conflict && lists) {  // exact only if no list position depended on an earlier push
-        if (list_read()) return fail(vm, XE_ERR_DEVICE, "list run");
-        for (int i = 0; i < 64; i++)
-          if (lr.sens[i] > lr.push[i]) list_conflict = true;
-        if (list_conflict) {
-          conflict = true;
-          // Segments: the packets before the first position that may have depended on an earlier push
-          // ran exactly; from there on the batch is a batch of its own whose start contents hold those
-          // pushes. The cut: per list, its first such packet (its first packet with a position, when that
-          // comes at or after its first push; else its first push, before which nothing was pushed).
-          // (Any cut keeps the packet loop's order — two batches are the same loop — so a pass that also
-          // ran out of an ordered map's room still cuts: each segment grows the room itself. A lane that
-          // needed an ordered map write elsewhere would need the fallback in every segment: no cut.)
-          if (!(flags & XE_FLAG_ORDERED)) {
-            seg_cut = n;
-            for (int i = 0; i < 64; i++)
-              if (lr.sens[i] > lr.push[i]) seg_cut = std::min(seg_cut, lr.senslo[i] >= lr.push[i] ? lr.senslo[i] : lr.push[i]);
-          }
-          flags |= XE_FLAG_ORDERED;
-        }
-      }
-      // appends past an ordered map's device room: the atomics counted every attempted append, so the
-      // room grows to what the batch needs and the parallel pass runs once more (up to three times: a
-      // count pass stops its packets at their first pop, so its appends undercount the ranked pass's)
-      if (ordmaps && attempt < 3 && (flags & XE_FLAG_CAPACITY) && !(flags & XE_FLAG_ORDERED)) {
-        const int g = ordered_grow(vm, ord_h0, s);
-        if (g < 0) return fail(vm, XE_ERR_DEVICE, "ordered map room");
-        if (g == 1) {
-          if (rollback(false) || prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
-          P.maps = vm->d_maps;
-          continue;
-        }
-      }
-      break;
-    }
-    // (a segment costs a pass over what follows it: at least kSegMin packets, else the usual fallback)
-    tmark("passes done");
-    if (conflict && mode == XE_MODE_AUTO && seg_cut >= kSegMin && seg_cut < n && segments_ok(vm, P)) {
-      if (rollback(false) || (ordmaps && ordered_hdr_restore(vm, ord_h0, s))) return fail(vm, XE_ERR_DEVICE, "rollback");
-      return run_segments(vm, d_umem, umem_len, d_desc, n, seg_cut, d_results, d_verdicts, d_regs, stream, stats);
-    }
-    if (conflict && (mode == XE_MODE_AUTO || (flags & XE_FLAG_CAPACITY))) {
-      // order-dependent batch (or a lane out of arena): roll the maps back; map-entry writes take the
-      // keyed path, everything else (and what the keyed path refuses) the replay in packet order.
-      // A pass that also ran out of an ordered map's room (appends beside an ordered write) grows it
-      // first, so the keyed path does not inherit the shortage.
-      bool grown = false;
-      if (ordmaps && (flags & XE_FLAG_CAPACITY) && (flags & XE_FLAG_ORDERED)) {
-        const int g = ordered_grow(vm, ord_h0, s);  // (restores the ordered maps itself)
-        if (g < 0) return fail(vm, XE_ERR_DEVICE, "ordered map room");
-        grown = g == 1;
-      }
-      if (rollback(false)) return fail(vm, XE_ERR_DEVICE, "rollback");
-      if (grown) {
-        if (prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
-        P.maps = vm->d_maps;
-      } else if (ordmaps) {  // the appends of the run are past the restored counts: unreferenced
-        if (ordered_hdr_restore(vm, ord_h0, s)) return fail(vm, XE_ERR_DEVICE, "rollback (ordered maps)");
-      }
-      int r = 1;
-      const bool try_keyed = keyed_ok && (flags & XE_FLAG_ORDERED) && (!(flags & XE_FLAG_CAPACITY) || grown) && !list_conflict;
-      if (try_keyed && vm->keyed_backoff) vm->keyed_backoff--;
-      else if (try_keyed) {
-        vm->t2.rec(s);
-        r = keyed(used);
-        for (int t = 0; r == 2 && t < 3; t++) r = keyed(used);  // its D table / an LRU pool was too small
-        if (r == 2) r = 1;
-        if (r < 0) return r;
-        if (r == 1) vm->keyed_backoff = kKeyedBackoff;
-        if (r == 0) {
-          vm->t1.rec(s);
-          if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "sync");
-          kms += Timer::ms(vm->t2, vm->t1);
-        }
-      }
-      if (r == 1) {
-        if (ordmaps) vm->ord_backoff = kKeyedBackoff;
-        used = XE_MODE_SEQUENTIAL;
-        if (int rc = sequential(kms)) return rc;
-      }
-    } else if (!conflict) {
-      vm->keyed_backoff = 0;
-      // the run's results stand: its appends into packet order, then its pops off the popped list (a
-      // stack's pushes all came after its pops, so they land on the lowered top)
-      if (ordmaps) {
-        std::vector<uint64_t> h0 = ord_h0;
-        std::vector<std::pair<uint32_t, uint64_t>> took;  // (list, its elements the batch popped)
-        if (popped) {
-          uint32_t last_used = 0;
-          if (d2h(&last_used, vm->d_popused + (n - 1), 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pop count");
-          uint32_t j = 0;
-          for (uint32_t mi = 0; mi < 64; mi++) {
-            if (!((popped >> mi) & 1)) continue;
-            uint32_t base = 0;
-            if (d2h(&base, vm->d_popbase + size_t(j) * n + (n - 1), 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pop count");
-            const uint64_t k = std::min<uint64_t>(uint64_t(base) + ((last_used >> (8 * j)) & 0xffu), ord_h0[mi * 8 + 1]);
-            if (vm->maps[mi].stack) h0[mi * 8 + 1] -= k;
-            if (k) took.push_back({mi, k});
-            j++;
-          }
-        }
-        tmark("before finalize");
-        if (ordered_finalize(vm, h0, n, s)) return fail(vm, XE_ERR_DEVICE, "ordered map appends");
-        tmark("finalize");
-        for (const auto& t : took) {
-          HostMap& m = vm->maps[t.first];
-          const uint64_t k = t.second;
-          uint64_t hdr[8];
-          if (d2h(hdr, m.d_hdr, 64, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pops");
-          if (!m.stack) hdr[0] = (hdr[0] + k) % m.list_cap;
-          hdr[1] -= k;
-          if (h2d(m.d_hdr, hdr, 64, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pops");
-        }
+    for (size_t i = 1; i < vm->maps.size(); i++) {  // the ordered maps come back from their rollback point:
+      HostMap& m = vm->maps[i];                       // an LRU map's device snapshot, the others' host mirror
+      if (m.dkind == XE_DM_LRU && m.dsnap) {
+        if (lru_dev_restore(m, s)) return -1;
+      } else if (m.ordered() && ordered_upload(vm, m, vm->ord_slack, vm->ord_slack_bytes)) {
+        return -1;
       }
     }
   }
+  if (keep_pkts && d2d(d_umem, vm->d_usnap, umem_len, s)) return -1;
+  return dmemset(vm->d_aux, 0, aux_used * 8, s);
+}
+
+// rollback point of what the parallel pass never writes: hash slot records (+ counts)
+int BatchRun::snap_records() {
+  std::vector<HashSnap> snaps;
+  const uint64_t kb = hash_snapshot_layout(vm, snaps);
+  if (kb && ensure_buf((void**)&vm->d_ksnap, &vm->d_ksnap_bytes, kb)) return fail(vm, XE_ERR_DEVICE, "device alloc (snapshot)");
+  for (const HashSnap& h : snaps) {
+    uint8_t* at = (uint8_t*)vm->d_ksnap + h.off;
+    if (d2d(at, h.m->d_keys, h.rb, s) || d2d(at + h.rb, h.m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, "snapshot");
+  }
+  return XE_OK;
+}
+
+// fold the 8-byte-add replicas into the value regions (and zero them for the next run)
+int BatchRun::fold() {
+  for (size_t i = 1; i < vm->maps.size(); i++) {
+    HostMap& m = vm->maps[i];
+    if (m.nrep > 1 && fold_map(m, s)) return -1;
+    if (m.dkind == XE_DM_LRU && m.trep_r > 1 && launch_lru_tag_fold(m.d_tag, m.d_trep, m.pool_cap, m.trep_r, m.d_hdr, s)) return -1;
+  }
+  return 0;
+}
+
+// The exact ordered replay: one lane walks the packets in order. Its arena (and the ordered maps'
+// room) grows x4 and the replay restarts from the rollback point whenever it runs out. Its kernel time
+// is added to kms.
+int BatchRun::sequential() {
+  // rollback point of what the parallel pass never writes: hash slot records, the ordered maps
+  if (int rc = snap_records()) return rc;
+  if (int rc = ordered_rollback_point(vm, s)) return rc;
+  // the replay lane's packets are staged 64 at a time by the whole wave unless a packet may write
+  // packet bytes a later packet reads (its window must then be fetched after the earlier writes)
+  P.seq_prefetch = may_write_packet(vm->programs[vm->entry]) ? 0u : 1u;
+  // and run ahead of the lane (per-program kernels; XE_SEQ_PEEK=0 in the tuning build: A/B)
+  if (P.seq_prefetch) {
+    const char* pk = xe_tuning_env("XE_SEQ_PEEK");
+    if (!pk || atoi(pk)) P.seq_prefetch |= 2u;
+  }
+  for (int attempt = 0;; attempt++) {
+    P.mode = XE_MODE_SEQUENTIAL;
+    if (general && ensure_arena(vm, true, 1, P.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (replay arena)");
+    bool table = false;  // the LRU maps' order logs from their stamps (the run's start state)
+    for (size_t i = 1; i < vm->maps.size(); i++) {
+      if (vm->maps[i].dkind != XE_DM_LRU) continue;
+      const int r = lru_log_build(vm, vm->maps[i], s);
+      if (r < 0) return fail(vm, XE_ERR_DEVICE, "LRU order log");
+      table = table || r > 0;
+    }
+    if (table) {
+      if (int rc = upload_map_table(vm, s)) return rc;
+      P.maps = vm->d_maps;
+    }
+    vm->t1.rec(s);
+    // a long replay on the scalar variant of the per-program kernel (every lane runs the packet)
+    void* sj = (jit && !jit_general && n >= kSeqScalarMin) ? variant_kernel(vm, jit, kSeqVariant) : nullptr;
+    if (launch_emulator(sj ? sj : jit, &P, 1, 64, s)) return fail(vm, XE_ERR_DEVICE, "kernel launch");
+    vm->t2.rec(s);
+    if (hostcalls && serve_hostcalls(vm->h_hostcall, s)) return fail(vm, XE_ERR_DEVICE, "kernel failed (host helpers)");
+    if (read_aux()) return fail(vm, XE_ERR_DEVICE, "kernel failed");
+    kms += Timer::ms(vm->t1, vm->t2);
+    if (!(red[0] & XE_FLAG_CAPACITY)) {
+      for (size_t i = 1; i < vm->maps.size(); i++)  // the replay kept stamps and its log, not the links
+        if (vm->maps[i].dkind == XE_DM_LRU) vm->maps[i].links_stale = true;
+      return XE_OK;
+    }
+    if (attempt >= 6) return fail(vm, XE_ERR_NOMEM, "the ordered replay outgrew its device arena");
+    vm->seq_scale *= 4;
+    vm->ord_slack *= 4;
+    vm->ord_slack_bytes *= 4;
+    if (rollback(true)) return fail(vm, XE_ERR_DEVICE, "rollback");
+    // the ordered maps' room grows with the slack: an LRU map, back at its start state on the device,
+    // goes through the host mirror into a larger pool, and that becomes the next attempt's rollback point
+    for (size_t i = 1; i < vm->maps.size(); i++) {
+      HostMap& m = vm->maps[i];
+      if (m.dkind != XE_DM_LRU) continue;
+      m.dev_dirty = true;
+      if (map_download(vm, m)) return fail(vm, XE_ERR_DEVICE, "map download");
+      m.host_dirty = true;
+    }
+    if (prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
+    for (size_t i = 1; i < vm->maps.size(); i++)
+      if (vm->maps[i].dkind == XE_DM_LRU && lru_dev_snapshot(vm->maps[i], s)) return fail(vm, XE_ERR_DEVICE, "LRU snapshot");
+    P.maps = vm->d_maps;
+  }
+}
+
+// ---- keyed ordered execution (xe_internal.h): the SPEC pass, the build, the parallel pass of the packets
+// on no chain, the chains. `used` on Done: XE_MODE_PARALLEL when no packet wrote a map entry, so the SPEC
+// pass was an ordinary parallel run; else XE_MODE_KEYED.
+
+// back to the attempt's start before any record was claimed (the cheaper rollback: map values, packets,
+// the ordered maps' header words / LRU value pools from kh0)
+int BatchRun::krollback() {
+  if (rollback(false)) return -1;
+  return ordmaps ? ordered_hdr_restore(vm, kh0, s) : 0;
+}
+
+// the attempt gives the batch to the one-lane replay: rolled back (hash_records: slot records were
+// claimed, so those and the ordered maps come back too)
+KeyedResult BatchRun::kreplay(const char* why, bool hash_records) {
+  keyed_trace(why);
+  if (hash_records ? rollback(true) : krollback()) return kerror();
+  return KeyedResult::Replay;
+}
+
+// 1. SPEC: every packet against the start state, writes held back, keys logged
+KeyedResult BatchRun::keyed_spec(bool& finished) {
+  finished = false;
+  kjit = variant_kernel(vm, jit, kKeyedVariant);
+  if (jit && !kjit) return KeyedResult::Replay;
+  // D table: 4x the last keyed batch's D keys (first time: n / 4), at most 2n (D holds <= n keys)
+  dmax = 4096, dcap = 4096;
+  while (dmax < 2ull * n && dmax < (1u << 30)) dmax <<= 1;
+  const uint64_t dwant = vm->keyed_dnext ? vm->keyed_dnext : std::max<uint64_t>(4096, n / 4);
+  while (dcap < dwant && dcap < dmax) dcap <<= 1;
+  tmark("keyed start");
+  if (keyed_alloc(vm, n, dcap)) return kfail(XE_ERR_NOMEM, "device alloc (keyed execution)");
+  tmark("keyed alloc");
+  // ordered maps (LRU_HASH keys, appends): the host mirror holds the batch's start (rollback(true)
+  // rebuilds the device copies from it), kh0 their header words / LRU value pools for the cheaper
+  // rollbacks before any record was claimed
+  kh0.clear();
+  if (ordmaps) {
+    if ((err = ordered_rollback_point(vm, s))) return KeyedResult::Error;
+    tmark("map snapshot");
+    if (ordered_hdr_read(vm, kh0, s)) return kfail(XE_ERR_DEVICE, "ordered map header");
+    tmark("hdr read");
+  }
+  K = vm->kd;
+  K.n = n;
+  if (dmemset(K.dkid, 0, uint64_t(K.dcap) * 8, s) || dmemset(vm->d_ksmall, 0, XE_KS_WORDS * 4, s) ||
+      dmemset(K.dfirst, 0xff, uint64_t(K.dcap) * 4, s) || dmemset(K.dvict, 0xff, uint64_t(K.dcap) * 4, s))
+    return kfail(XE_ERR_DEVICE, "keyed reset");
+  kgrid = parallel_grid(vm, kjit, general, n, P.nmaps);
+  X = P;
+  if (general && ensure_arena(vm, false, kgrid * 256, X.gen)) return kfail(XE_ERR_NOMEM, "device alloc (arena)");
+  tmark("arena");
+  X.mode = XE_MODE_SPEC;
+  X.K = K;
+  if (launch_emulator(kjit, &X, kgrid, 256, s) || fold()) return kfail(XE_ERR_DEVICE, "kernel launch (keyed spec)");
+  if (read_aux()) return kfail(XE_ERR_DEVICE, "kernel failed (keyed spec)");
+  const uint32_t sflags = uint32_t(red[0]);
+  if (ordmaps && (sflags & XE_FLAG_CAPACITY) && !(sflags & XE_FLAG_ORDERED)) {
+    // appends past an ordered map's device room (the parallel branch's ordered_grow): the room
+    // grows to what the pass tried to append and the keyed path starts over
+    const int g = ordered_grow(vm, kh0, s);
+    if (g < 0) return kfail(XE_ERR_DEVICE, "ordered map room");
+    if (g == 1) {
+      if (rollback(false) || prepare_run(vm, s)) return kfail(XE_ERR_DEVICE, "rollback");
+      P.maps = vm->d_maps;
+      keyed_trace("spec capacity: grown");
+      return KeyedResult::Retry;
+    }
+  }
+  if (sflags & (XE_FLAG_ORDERED | XE_FLAG_CAPACITY)) return kreplay("spec ordered/capacity");
+  if (!(sflags & XE_FLAG_KEYED)) {  // no packet wrote a map entry: an ordinary parallel run
+    if (run_conflict(red, P.nmaps)) return kreplay("spec conflict");
+    if (ordmaps && ordered_finalize(vm, kh0, n, s)) return kfail(XE_ERR_DEVICE, "ordered map appends");
+    used = XE_MODE_PARALLEL;
+    finished = true;
+  }
+  return KeyedResult::Done;
+}
+
+// 2. build: D, chains (union-find rounds), each packet's chain
+KeyedResult BatchRun::keyed_build() {
+  small.assign(XE_KS_WORDS, 0);
+  if (kstep(XE_KS_DSET, n)) return kfail(XE_ERR_DEVICE, "keyed build");
+  for (int round = 0;; round++) {
+    if (round >= 64) return kreplay("union rounds");
+    if (dmemset(K.changed, 0, 4, s) || kstep(XE_KS_UNION, n) || read_small()) return kfail(XE_ERR_DEVICE, "keyed build");
+    if (!small[XE_KS_CHANGED]) break;
+  }
+  if (kstep(XE_KS_COMPRESS, K.dcap) || kstep(XE_KS_ASSIGN, n) || kstep(XE_KS_COUNT, K.dcap) || read_small())
+    return kfail(XE_ERR_DEVICE, "keyed build");
+  if (small[XE_KS_ERR] & 8u) {  // D outgrew its table: once more with room for every packet's key
+    vm->keyed_dnext = dmax;
+    if (dcap < dmax) {
+      keyed_trace("D full");
+      if (krollback()) return kerror();
+      return KeyedResult::Retry;
+    }
+  }
+  // key log overflow (1), a root walk that did not end (16): the in-order replay
+  if (small[XE_KS_ERR]) return kreplay(small[XE_KS_ERR] & 16u ? "root walk" : "key log overflow");
+  uint64_t nd = 0;
+  for (uint32_t i = 0; i < 64; i++) nd += small[XE_KS_DCOUNT + i];
+  uint64_t next = 4096;
+  while (next < 4 * nd && next < dmax) next <<= 1;
+  vm->keyed_dnext = uint32_t(next);
+  return KeyedResult::Done;
+}
+
+// 3. capacity: a HASH insert can fail for capacity only in an order-dependent way (and an LRU insert
+// would evict by the batch's order of touches): every key some packet inserts fits. Only an absent key's
+// insert meets the capacity rule (maps_hash.go:84-89, maps_hash_lru.go:114-119) and nothing deletes in a
+// keyed batch, so the bound is the live count + the D keys a packet inserts (XE_KS_DINS); keys that are
+// only looked up, promoted or updated in place do not count
+KeyedResult BatchRun::keyed_capacity() {
+  evict.clear();
+  for (size_t i = 1; i < vm->maps.size() && i < 64; i++) {
+    HostMap& m = vm->maps[i];
+    const uint64_t nd = small[XE_KS_DINS + i];
+    if ((m.dkind != XE_DM_HASH && m.dkind != XE_DM_LRU) || !nd) continue;
+    uint64_t cnt = 0;
+    if (m.dkind == XE_DM_HASH) {
+      uint32_t c32 = 0;
+      if (d2h(&c32, m.d_count, 4, s) || dsync(s)) return kfail(XE_ERR_DEVICE, "count");
+      cnt = c32;
+    } else {
+      cnt = kh0[i * 8 + 2];
+      // value ids for every new key that does not take over its victim's (keyed_lruid_item): grow the
+      // pool and run again
+      const uint64_t ev = cnt + nd > m.def.max_entries ? cnt + nd - m.def.max_entries : 0;
+      if (kh0[i * 8 + 3] + (nd - ev) > m.pool_cap) {
+        if (krollback() || map_download(vm, m)) return kerror();  // the mirror: the batch's start
+        vm->ord_slack = std::max<uint64_t>(vm->ord_slack, 2 * nd + 4096);
+        m.host_dirty = true;  // rebuilt from the mirror with the larger pool
+        if (prepare_run(vm, s)) return kfail(XE_ERR_DEVICE, "ordered map room");
+        P.maps = vm->d_maps;
+        keyed_trace("LRU pool grown");
+        return KeyedResult::Retry;
+      }
+    }
+    if (cnt + nd > m.def.max_entries) {
+      if (m.dkind != XE_DM_LRU) return kreplay("capacity");
+      evict[i] = cnt + nd - m.def.max_entries;  // the batch's inserts evict: planned by keyed_evictions
+    }
+  }
+  return KeyedResult::Done;
+}
+
+// 4. LRU evictions (xe_interp.h keyed_evict_item): rank every LRU map's new keys by their first
+// inserting packet, give the inserts past the map's room the oldest values of the batch's start as
+// victims, and replay in order if any packet of the batch touches one of them
+KeyedResult BatchRun::keyed_evictions() {
+  if (evict.empty()) return KeyedResult::Done;
+  size_t eb = 0;
+  if (kstep(XE_KS_FIRST, n) || kstep(XE_KS_EKEY, K.dcap) || launch_keyed_esort(&K, nullptr, &eb, s) ||
+      ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, eb) || launch_keyed_esort(&K, vm->d_ksort, &eb, s))
+    return kfail(XE_ERR_DEVICE, "keyed evictions");
+  uint64_t off = 0;
+  for (size_t i = 1; i < vm->maps.size() && i < 64; i++) {
+    HostMap& m = vm->maps[i];
+    if (m.dkind != XE_DM_LRU) continue;
+    const uint32_t nd = small[XE_KS_DINS + i];
+    if (evict.count(i)) {
+      const uint64_t cnt = kh0[i * 8 + 2];
+      // the start's UsageList by stamp (the stamps at the batch's start: the snapshot of ordered_hdr_read)
+      size_t rb = 0;
+      if (launch_lru_relink(m.d_tsnap, m.pool_cap, uint32_t(cnt), m.d_link, m.d_hdr, nullptr, &rb, 2, s) ||
+          ensure_buf(&vm->d_relink, &vm->d_relink_cap, rb) ||
+          launch_lru_relink(m.d_tsnap, m.pool_cap, uint32_t(cnt), m.d_link, m.d_hdr, vm->d_relink, &rb, 2, s))
+        return kfail(XE_ERR_DEVICE, "keyed evictions (order)");
+      K.em = uint32_t(i);
+      K.eoff = uint32_t(off);
+      K.efree = uint32_t(m.def.max_entries - cnt);
+      K.ecnt0 = uint32_t(cnt);
+      K.etsnap = m.d_tsnap;
+      K.vorder = lru_sorted_ids(vm->d_relink, m.pool_cap);
+      if (kstep(XE_KS_EVICT, nd) || kstep(XE_KS_EMARK, nd)) return kfail(XE_ERR_DEVICE, "keyed evictions");
+    }
+    off += nd;
+  }
+  if (read_small()) return kfail(XE_ERR_DEVICE, "keyed evictions");
+  if (small[XE_KS_ERR] & 8u) {  // the victims' keys did not fit the D table
+    vm->keyed_dnext = dmax;
+    if (dcap < dmax) {
+      keyed_trace("D full (victims)");
+      if (krollback()) return kerror();
+      return KeyedResult::Retry;
+    }
+  }
+  if (small[XE_KS_ERR]) return kreplay("eviction seen by the batch");
+  K.em = 0;
+  return KeyedResult::Done;
+}
+
+// 5. the packets sorted by chain, the chains' starts; a batch with one long chain replays in order
+KeyedResult BatchRun::keyed_order() {
+  uint32_t end_bit = 1;
+  while ((1ull << end_bit) <= K.dcap) end_bit++;
+  size_t sb = 0;
+  if (kstep(XE_KS_IOTA, n) || launch_keyed_sort(&K, n, end_bit, nullptr, &sb, s) ||
+      ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, sb) || launch_keyed_sort(&K, n, end_bit, vm->d_ksort, &sb, s))
+    return kfail(XE_ERR_DEVICE, "keyed sort");
+  if (kstep(XE_KS_NCHAIN, n) || read_small()) return kfail(XE_ERR_DEVICE, "keyed build");
+  K.nO = small[XE_KS_NO];
+  // one chain with more than half the packets (a hot key written by most of them): its lane would
+  // take longer than the staged one-lane replay of the whole batch
+  if (kstep(XE_KS_CSTART, K.nO) || kstep(XE_KS_CLONG, K.nO) || read_small()) return kfail(XE_ERR_DEVICE, "keyed build");
+  if (small[XE_KS_LONG]) return kreplay("long chain");
+  return KeyedResult::Done;
+}
+
+// 6. back to the start state; reserve a slot record for every new HASH key of D
+KeyedResult BatchRun::keyed_reserve() {
+  if (krollback() || snap_records()) return kfail(XE_ERR_DEVICE, "rollback");
+  if (ordmaps && kstep(XE_KS_LRUID, K.dcap)) return kfail(XE_ERR_DEVICE, "keyed value ids");
+  if (kstep(XE_KS_RESERVE, K.dcap) || read_small()) return kfail(XE_ERR_DEVICE, "keyed reserve");
+  if (small[XE_KS_ERR]) return kreplay("reserve", true);
+  return KeyedResult::Done;
+}
+
+// 7. the packets on no chain, in parallel (the fast kernel: the skip mask is its only keyed input)
+KeyedResult BatchRun::keyed_remainder() {
+  X.mode = XE_MODE_PARALLEL;
+  X.K = K;
+  X.K.skip = vm->d_skip;
+  if (K.nO < n) {
+    XeParams Y = X;
+    const uint32_t pgrid = parallel_grid(vm, jit, general, n, P.nmaps);
+    if (general && ensure_arena(vm, false, pgrid * 256, Y.gen)) return kfail(XE_ERR_NOMEM, "device alloc (arena)");
+    if (launch_emulator(jit, &Y, pgrid, 256, s) || fold()) return kfail(XE_ERR_DEVICE, "kernel launch (keyed parallel)");
+  }
+  return KeyedResult::Done;
+}
+
+// 8. the chains in packet order: the compacted chain list is a work queue the waves claim from; then
+// the chains' inserts into the map counts, the appends and LRU touches into packet order
+KeyedResult BatchRun::keyed_chains() {
+  {
+    size_t sb2 = 0;
+    if (kstep(XE_KS_CFLAG, K.nO) || launch_keyed_scan(&K, K.nO, nullptr, &sb2, s) ||
+        ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, sb2) || launch_keyed_scan(&K, K.nO, vm->d_ksort, &sb2, s) ||
+        kstep(XE_KS_CLIST, K.nO) || dmemset(vm->d_ksmall + XE_KS_CNEXT, 0, 4, s))
+      return kfail(XE_ERR_DEVICE, "keyed chain list");
+  }
+  X.mode = XE_MODE_CHAIN;
+  X.K.skip = nullptr;
+  const uint32_t cgrid = std::max<uint32_t>(1, std::min<uint32_t>(kgrid, (K.nO + 255) / 256));
+  if (general && ensure_arena(vm, false, cgrid * 256, X.gen)) return kfail(XE_ERR_NOMEM, "device alloc (arena)");
+  if (launch_emulator(kjit, &X, cgrid, 256, s) || kstep(XE_KS_UNNEW, K.dcap)) return kfail(XE_ERR_DEVICE, "kernel launch (keyed chains)");
+  if (read_aux() || read_small()) return kfail(XE_ERR_DEVICE, "kernel failed (keyed chains)");
+  if (run_conflict(red, P.nmaps)) return kreplay("chain conflict", true);  // a packet left its chain / an order-dependent add
+  // the chains' inserts into the map counts (LRU_HASH: header word 2, less its evictions). An LRU map
+  // with evictions must have seen every ranked insert: one that did not happen shifts the victims of
+  // the inserts after it
+  auto inserts = [&](size_t i) {
+    uint32_t add = 0;
+    for (uint32_t k = 0; k < XE_KSTRIPES; k++) add += small[XE_KS_CINS + i * XE_KSTRIPES + k];
+    return add;
+  };
+  for (const auto& [i, ev] : evict)
+    if (inserts(i) != small[XE_KS_DINS + i]) return kreplay("eviction ranks", true);
+  for (size_t i = 1; i < vm->maps.size() && i < 64; i++) {
+    HostMap& m = vm->maps[i];
+    const uint32_t add = inserts(i);
+    if (!add) continue;
+    if (m.dkind == XE_DM_HASH) {
+      uint32_t cnt = 0;
+      if (d2h(&cnt, m.d_count, 4, s) || dsync(s)) return kfail(XE_ERR_DEVICE, "count");
+      cnt += add;
+      if (h2d(m.d_count, &cnt, 4, s) || dsync(s)) return kfail(XE_ERR_DEVICE, "count");
+    } else if (m.dkind == XE_DM_LRU) {
+      uint64_t cnt = 0;
+      if (d2h(&cnt, m.d_hdr + 2, 8, s) || dsync(s)) return kfail(XE_ERR_DEVICE, "count");
+      cnt += add;
+      if (evict.count(i)) cnt -= evict[i];
+      if (h2d(m.d_hdr + 2, &cnt, 8, s) || dsync(s)) return kfail(XE_ERR_DEVICE, "count");
+    }
+  }
+  // the appends and LRU touches of both passes into packet order
+  if (ordmaps && ordered_finalize(vm, kh0, n, s)) return kfail(XE_ERR_DEVICE, "ordered map appends");
+  vm->last_grid = kgrid;
+  used = XE_MODE_KEYED;
+  return KeyedResult::Done;
+}
+
+// one keyed attempt
+KeyedResult BatchRun::keyed() {
+  bool finished = false;  // no packet wrote a map entry: the SPEC pass was an ordinary parallel run
+  KeyedResult r = keyed_spec(finished);
+  if (r != KeyedResult::Done || finished) return r;
+  if ((r = keyed_build()) != KeyedResult::Done) return r;
+  if ((r = keyed_capacity()) != KeyedResult::Done) return r;
+  if ((r = keyed_evictions()) != KeyedResult::Done) return r;
+  if ((r = keyed_order()) != KeyedResult::Done) return r;
+  if ((r = keyed_reserve()) != KeyedResult::Done) return r;
+  if ((r = keyed_remainder()) != KeyedResult::Done) return r;
+  return keyed_chains();
+}
+
+// ... started over up to three times when its D table / an LRU pool was too small; then the replay
+KeyedResult BatchRun::keyed_with_retries() {
+  KeyedResult r = keyed();
+  for (int t = 0; r == KeyedResult::Retry && t < 3; t++) r = keyed();
+  return r == KeyedResult::Retry ? KeyedResult::Replay : r;
+}
+
+// the last batch wrote map entries: straight to the keyed path (and from there, when it refuses, in order)
+int BatchRun::keyed_first() {
+  const KeyedResult r = keyed_with_retries();
+  if (r == KeyedResult::Error) return err;
+  if (r == KeyedResult::Replay) {
+    vm->keyed_backoff = kKeyedBackoff;
+    if (ordmaps) vm->ord_backoff = kKeyedBackoff;
+    if (int rc = replay_in_order()) return rc;
+  }
+  conflict = used != XE_MODE_PARALLEL;
+  vm->t1.rec(s);
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "sync");
+  kms += Timer::ms(vm->t0, vm->t1);
+  return XE_OK;
+}
+
+// ---- the parallel passes
+
+// QUEUE / STACK pops, peeks and lookups in parallel (xe_interp.h list_pos): the run's list record,
+// and for a program that may pop, the buffers of the count pass (which packets pop: their prefix sum is
+// each pop's rank in packet order)
+int BatchRun::list_setup() {
+  lists = ordmaps && n > 0 && has_list_maps(vm);
+  pops = lists && may_pop(vm);
+  if (!lists) return XE_OK;
+  if (!vm->d_listrun && dev_alloc((void**)&vm->d_listrun, sizeof(XeListRun))) return fail(vm, XE_ERR_NOMEM, "device alloc (lists)");
+  P.list = vm->d_listrun;
+  if (pops && vm->pop_n < n) {
+    dev_free(vm->d_popflag); dev_free(vm->d_popbase); dev_free(vm->d_popused);
+    vm->d_popflag = vm->d_popbase = vm->d_popused = nullptr;
+    vm->pop_n = 0;
+    if (dev_alloc((void**)&vm->d_popflag, size_t(n) * 4) || dev_alloc((void**)&vm->d_popbase, size_t(n) * 4 * XE_POP_SLOTS) ||
+        dev_alloc((void**)&vm->d_popused, size_t(n) * 4))
+      return fail(vm, XE_ERR_NOMEM, "device alloc (pop ranks)");
+    vm->pop_n = n;
+  }
+  return XE_OK;
+}
+
+// the list record of a pass: start counts from the headers, no sensitive op, no push yet
+int BatchRun::list_init() {
+  memset(&lr, 0, sizeof lr);
+  for (size_t i = 1; i < vm->maps.size() && i < 64; i++)
+    if (vm->maps[i].dkind == XE_DM_LIST) lr.cnt0[i] = uint32_t(ord_h0[i * 8 + 1]);
+  for (int i = 0; i < 64; i++) lr.push[i] = lr.senslo[i] = 0xffffffffu;
+  return h2d(vm->d_listrun, &lr, sizeof lr, s);
+}
+
+// one parallel pass over the batch: kernel, replica fold, records (kms, flags, conflict)
+int BatchRun::pass() {
+  if (launch_emulator(pj, &P, vm->last_grid, 256, s)) return fail(vm, XE_ERR_DEVICE, "kernel launch");
+  vm->t1.rec(s);  // kernel_ms: the emulator kernel alone
+  if (fold()) return fail(vm, XE_ERR_DEVICE, "replica fold");
+  if (read_aux()) return fail(vm, XE_ERR_DEVICE, "kernel failed");
+  kms = Timer::ms(vm->t0, vm->t1);
+  flags = uint32_t(red[0]);
+  conflict = run_conflict(red, P.nmaps);
+  return XE_OK;
+}
+
+// A program that may pop: a count pass first, then the pass proper from the batch's start again.
+// Ranked passes: each popped list gets a slot; a packet's pops of it are counted in 8 bits of its
+// word (the count pass's first pops, then what the last ranked pass observed), the counts of each
+// slot are scanned into ranks, and the pass runs again from the batch's start until every packet
+// made exactly the pops it was ranked by (a pop after a peek, a second pop, or pops from another
+// list change what the count pass saw). Up to 4 passes; then, or with more than XE_POP_SLOTS
+// popped lists, the batch replays in order.
+int BatchRun::ranked_passes() {
+  P.pop_mode = 1;
+  P.popflag = vm->d_popflag;
+  P.popbase = nullptr;
+  if (dmemset(vm->d_popflag, 0, size_t(n) * 4, s)) return fail(vm, XE_ERR_DEVICE, "pop flags");
+  if (int rc = pass()) return rc;
+  tmark("count pass");
+  if (conflict) return XE_OK;
+  if (list_read()) return fail(vm, XE_ERR_DEVICE, "list run");
+  uint64_t mask = lr.popmask;
+  bool ranked = false;
+  for (int it = 0; it < 4 && !conflict; it++) {
+    if (__builtin_popcountll(mask) > int(XE_POP_SLOTS)) break;
+    XePopSlots sl;
+    memset(sl.slot, 0xff, sizeof sl.slot);
+    uint32_t ns = 0;
+    for (uint32_t m = 0; m < 64; m++)
+      if ((mask >> m) & 1) sl.slot[m] = uint8_t(ns++);
+    memcpy(P.pop_slot, sl.slot, sizeof sl.slot);
+    P.pop_stride = n;
+    // the counts to rank by: packed count-pass flags first, then the last pass's observed counts
+    if (it == 0 ? launch_pop(vm->d_popflag, vm->d_popused, n, 0, 0, sl, nullptr, s)
+                : d2d(vm->d_popused, vm->d_popflag, size_t(n) * 4, s))
+      return fail(vm, XE_ERR_DEVICE, "pop ranks");
+    for (uint32_t j = 0; j < ns; j++) {
+      XeKeyed S{};
+      S.iota = vm->d_popflag;  // (free until the pass writes its observed counts)
+      S.ckey = vm->d_popbase + size_t(j) * n;
+      size_t sb = 0;
+      if (launch_pop(vm->d_popused, vm->d_popflag, n, 1, j, sl, nullptr, s) ||
+          launch_keyed_scan(&S, n, nullptr, &sb, s) || ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, sb) ||
+          launch_keyed_scan(&S, n, vm->d_ksort, &sb, s))
+        return fail(vm, XE_ERR_DEVICE, "pop ranks");
+    }
+    if (rollback(false) || ordered_hdr_restore(vm, ord_h0, s) || list_init()) return fail(vm, XE_ERR_DEVICE, "pop ranks");
+    tmark("ranks");
+    P.pop_mode = 2;
+    P.popbase = vm->d_popbase;
+    if (int rc = pass()) return rc;
+    tmark("ranked pass");
+    if (conflict) break;
+    if (list_read()) return fail(vm, XE_ERR_DEVICE, "list run");
+    if (lr.newlist) {  // a pop of a list with no slot: rank it too
+      mask |= lr.popmask;
+      continue;
+    }
+    if (ensure_buf(&vm->d_ksort, &vm->d_ksort_cap, 256)) return fail(vm, XE_ERR_NOMEM, "pop ranks");
+    uint32_t* d_flag = (uint32_t*)vm->d_ksort;  // (the scans' scratch, free now)
+    uint32_t mismatch = 0;
+    if (dmemset(d_flag, 0, 4, s) || launch_pop(vm->d_popflag, vm->d_popused, n, 2, 0, sl, d_flag, s) ||
+        d2h(&mismatch, d_flag, 4, s) || dsync(s))
+      return fail(vm, XE_ERR_DEVICE, "pop ranks");
+    if (!mismatch) {
+      ranked = true;
+      popped = mask;
+      break;
+    }
+  }
+  if (!ranked && !conflict) {
+    list_conflict = conflict = true;
+    flags |= XE_FLAG_ORDERED;
+  }
+  return XE_OK;
+}
+
+// After a pass without conflict: exact only if no list position depended on an earlier push. If one
+// did, the batch is order-dependent, and seg_cut says where it may be cut into segments.
+// Segments: the packets before the first position that may have depended on an earlier push
+// ran exactly; from there on the batch is a batch of its own whose start contents hold those
+// pushes. The cut: per list, its first such packet (its first packet with a position, when that
+// comes at or after its first push; else its first push, before which nothing was pushed).
+// (Any cut keeps the packet loop's order — two batches are the same loop — so a pass that also
+// ran out of an ordered map's room still cuts: each segment grows the room itself. A lane that
+// needed an ordered map write elsewhere would need the fallback in every segment: no cut.)
+int BatchRun::list_sensitivity() {
+  if (list_read()) return fail(vm, XE_ERR_DEVICE, "list run");
+  for (int i = 0; i < 64; i++)
+    if (lr.sens[i] > lr.push[i]) list_conflict = true;
+  if (!list_conflict) return XE_OK;
+  conflict = true;
+  if (!(flags & XE_FLAG_ORDERED)) {
+    seg_cut = n;
+    for (int i = 0; i < 64; i++)
+      if (lr.sens[i] > lr.push[i]) seg_cut = std::min(seg_cut, lr.senslo[i] >= lr.push[i] ? lr.senslo[i] : lr.push[i]);
+  }
+  flags |= XE_FLAG_ORDERED;
+  return XE_OK;
+}
+
+// The batch in parallel: one pass (count and ranked passes for a program that may pop), run again
+// with more room while only an ordered map's device room was short. Leaves conflict, flags, seg_cut.
+int BatchRun::parallel() {
+  P.mode = XE_MODE_PARALLEL;
+  pj = (jit && !P.results && !P.regs) ? variant_kernel(vm, jit, kLeanVariant) : jit;  // verdicts only: the lean variant
+  vm->last_grid = parallel_grid(vm, pj, general, n, P.nmaps);
+  if (general && ensure_arena(vm, false, vm->last_grid * 256, P.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (arena)");
+  if (int rc = list_setup()) return rc;
+  for (int attempt = 0;; attempt++) {
+    if (ordmaps && ordered_hdr_read(vm, ord_h0, s)) return fail(vm, XE_ERR_DEVICE, "ordered map header");
+    if (lists && list_init()) return fail(vm, XE_ERR_DEVICE, "list run");
+    tmark("ordered hdr");
+    if (int rc = pops ? ranked_passes() : pass()) return rc;
+    if (!conflict && lists)
+      if (int rc = list_sensitivity()) return rc;
+    // appends past an ordered map's device room: the atomics counted every attempted append, so the
+    // room grows to what the batch needs and the parallel pass runs once more (up to three times: a
+    // count pass stops its packets at their first pop, so its appends undercount the ranked pass's)
+    if (ordmaps && attempt < 3 && (flags & XE_FLAG_CAPACITY) && !(flags & XE_FLAG_ORDERED)) {
+      const int g = ordered_grow(vm, ord_h0, s);
+      if (g < 0) return fail(vm, XE_ERR_DEVICE, "ordered map room");
+      if (g == 1) {
+        if (rollback(false) || prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
+        P.maps = vm->d_maps;
+        continue;
+      }
+    }
+    break;
+  }
+  tmark("passes done");
+  return XE_OK;
+}
+
+// An order-dependent batch (or a lane out of arena): roll the maps back; map-entry writes take the
+// keyed path, everything else (and what the keyed path refuses) the replay in packet order.
+// A pass that also ran out of an ordered map's room (appends beside an ordered write) grows it
+// first, so the keyed path does not inherit the shortage.
+int BatchRun::after_conflict() {
+  bool grown = false;
+  if (ordmaps && (flags & XE_FLAG_CAPACITY) && (flags & XE_FLAG_ORDERED)) {
+    const int g = ordered_grow(vm, ord_h0, s);  // (restores the ordered maps itself)
+    if (g < 0) return fail(vm, XE_ERR_DEVICE, "ordered map room");
+    grown = g == 1;
+  }
+  if (rollback(false)) return fail(vm, XE_ERR_DEVICE, "rollback");
+  if (grown) {
+    if (prepare_run(vm, s)) return fail(vm, XE_ERR_DEVICE, "rollback");
+    P.maps = vm->d_maps;
+  } else if (ordmaps) {  // the appends of the run are past the restored counts: unreferenced
+    if (ordered_hdr_restore(vm, ord_h0, s)) return fail(vm, XE_ERR_DEVICE, "rollback (ordered maps)");
+  }
+  KeyedResult r = KeyedResult::Replay;
+  const bool try_keyed = keyed_ok && (flags & XE_FLAG_ORDERED) && (!(flags & XE_FLAG_CAPACITY) || grown) && !list_conflict;
+  if (try_keyed && vm->keyed_backoff) vm->keyed_backoff--;
+  else if (try_keyed) {
+    vm->t2.rec(s);
+    r = keyed_with_retries();
+    if (r == KeyedResult::Error) return err;
+    if (r == KeyedResult::Replay) vm->keyed_backoff = kKeyedBackoff;
+    if (r == KeyedResult::Done) {
+      vm->t1.rec(s);
+      if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "sync");
+      kms += Timer::ms(vm->t2, vm->t1);
+    }
+  }
+  if (r == KeyedResult::Replay) {
+    if (ordmaps) vm->ord_backoff = kKeyedBackoff;
+    return replay_in_order();
+  }
+  return XE_OK;
+}
+
+// the run's results stand: its appends into packet order, then its pops off the popped list (a
+// stack's pushes all came after its pops, so they land on the lowered top)
+int BatchRun::results_stand() {
+  vm->keyed_backoff = 0;
+  if (!ordmaps) return XE_OK;
+  std::vector<uint64_t> h0 = ord_h0;
+  std::vector<std::pair<uint32_t, uint64_t>> took;  // (list, its elements the batch popped)
+  if (popped) {
+    uint32_t last_used = 0;
+    if (d2h(&last_used, vm->d_popused + (n - 1), 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pop count");
+    uint32_t j = 0;
+    for (uint32_t mi = 0; mi < 64; mi++) {
+      if (!((popped >> mi) & 1)) continue;
+      uint32_t base = 0;
+      if (d2h(&base, vm->d_popbase + size_t(j) * n + (n - 1), 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pop count");
+      const uint64_t k = std::min<uint64_t>(uint64_t(base) + ((last_used >> (8 * j)) & 0xffu), ord_h0[mi * 8 + 1]);
+      if (vm->maps[mi].stack) h0[mi * 8 + 1] -= k;
+      if (k) took.push_back({mi, k});
+      j++;
+    }
+  }
+  tmark("before finalize");
+  if (ordered_finalize(vm, h0, n, s)) return fail(vm, XE_ERR_DEVICE, "ordered map appends");
+  tmark("finalize");
+  for (const auto& t : took) {
+    HostMap& m = vm->maps[t.first];
+    const uint64_t k = t.second;
+    uint64_t hdr[8];
+    if (d2h(hdr, m.d_hdr, 64, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pops");
+    if (!m.stack) hdr[0] = (hdr[0] + k) % m.list_cap;
+    hdr[1] -= k;
+    if (h2d(m.d_hdr, hdr, 64, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "pops");
+  }
+  return XE_OK;
+}
+
+// what the run leaves on the VM (hints, add widths, footprint, live counts) and in the caller's statistics
+int BatchRun::publish() {
   if (n > 0) vm->keyed_hint = used == XE_MODE_KEYED;  // (an empty batch, e.g. a map upload, says nothing)
   if (used == XE_MODE_KEYED) red[0] |= XE_FLAG_ORDERED;  // order-dependent effects (shard checks replay it)
   record_widths(vm, red, P.nmaps);
@@ -3426,18 +3548,47 @@ int xe_run_batch_device(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* 
   tmark("done");
   if (n > 0)  // an empty batch (a map upload) changes no map: the host mirrors stay current
     for (size_t i = 1; i < vm->maps.size(); i++) vm->maps[i].dev_dirty = true;
-  if (stats) {
-    stats->packets = n;
-    stats->steps = red[1];
-    for (int k = 0; k < 8; k++) stats->status_count[k] = red[2 + k];
-    stats->mode_used = used;
-    stats->conflict = conflict ? 1 : 0;
-    stats->kernel_ms = kms;
-    stats->total_ms = kms;
-    stats->engine_used = jit ? XE_ENGINE_JIT : XE_ENGINE_INTERP;
-    stats->grid_blocks = used == XE_MODE_SEQUENTIAL ? 1 : vm->last_grid;
-  }
+  publish_stats(stats, red, n, used, conflict, kms, jit ? XE_ENGINE_JIT : XE_ENGINE_INTERP,
+                used == XE_MODE_SEQUENTIAL ? 1 : vm->last_grid);
   return XE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One batch, synchronously: prepare; then in packet order straight away, keyed first, or in parallel;
+// a parallel run that turned out order-dependent goes on as packet-order segments, through the keyed
+// path, or in packet order; publish.
+int xe_run_batch_device(xe_vm* vm, void* d_umem, uint64_t umem_len, const void* d_desc, uint32_t n,
+                        void* d_results, void* d_verdicts, void* d_regs, void* stream, xe_batch_stats* stats) {
+  if (!vm) return XE_ERR_INVAL;
+  BatchRun b{vm, d_umem, umem_len, d_desc, n, d_results, d_verdicts, d_regs, stream, stats};
+  if (int rc = b.prepare()) return rc;
+  // ordered maps: appends and LRU lookups run in parallel (put in packet order afterwards), LRU updates
+  // through the keyed path; a batch with any other operation on them (pops, peeks, list lookups, an LRU
+  // eviction) replays in order, and so do the next few after such a batch
+  const bool automatic = b.mode == XE_MODE_AUTO;
+  const bool ord_par = !b.ordmaps || ordered_parallel_ok(vm);
+  b.keyed_ok = automatic && n > 0 && !b.overlap && ord_par;
+  const bool ord_seq = automatic && b.ordmaps && (!ord_par || vm->ord_backoff);
+  if (ord_seq && vm->ord_backoff) vm->ord_backoff--;
+  int rc = XE_OK;
+  if (b.mode == XE_MODE_SEQUENTIAL || ord_seq || b.overlap || b.hostcalls) {
+    rc = b.replay_in_order();
+  } else if (b.keyed_ok && vm->keyed_hint) {
+    rc = b.keyed_first();
+  } else {
+    if ((rc = b.parallel())) return rc;
+    // (a segment costs a pass over what follows it: at least kSegMin packets, else the usual fallback)
+    if (b.conflict && automatic && b.seg_cut >= kSegMin && b.seg_cut < n && segments_ok(vm, b.P)) {
+      if (b.rollback(false) || (b.ordmaps && ordered_hdr_restore(vm, b.ord_h0, b.s))) return fail(vm, XE_ERR_DEVICE, "rollback");
+      return run_segments(vm, d_umem, umem_len, d_desc, n, b.seg_cut, d_results, d_verdicts, d_regs, stream, stats);
+    }
+    if (b.conflict && (automatic || (b.flags & XE_FLAG_CAPACITY))) rc = b.after_conflict();
+    else if (!b.conflict) rc = b.results_stand();
+  }
+  return rc ? rc : b.publish();
 }
 
 namespace {
@@ -3474,17 +3625,9 @@ int complete_oldest(xe_vm* vm) {
   reduce_aux(aux, sl.nmaps, 16 + 2 * (sl.nmaps + 1), red);
   record_widths(vm, red, sl.nmaps);
   note_run(vm, red, XE_MODE_PARALLEL);
-  if (xe_batch_stats* st = sl.b.stats) {
-    st->packets = sl.b.n;
-    st->steps = red[1];
-    for (int k = 0; k < 8; k++) st->status_count[k] = red[2 + k];
-    st->mode_used = XE_MODE_PARALLEL;
-    st->conflict = run_conflict(red, sl.nmaps) ? 1 : 0;  // reported, not replayed (XE_MODE_PARALLEL)
-    st->kernel_ms = Timer::ms(sl.t0, sl.t1);
-    st->total_ms = st->kernel_ms;
-    st->engine_used = sl.engine;
-    st->grid_blocks = sl.grid;
-  }
+  if (sl.b.stats)  // a conflict is reported, not replayed (XE_MODE_PARALLEL)
+    publish_stats(sl.b.stats, red, sl.b.n, XE_MODE_PARALLEL, run_conflict(red, sl.nmaps), Timer::ms(sl.t0, sl.t1), sl.engine,
+                  sl.grid);
   vm->pending.erase(vm->pending.begin());
   return XE_OK;
 }
@@ -3501,8 +3644,8 @@ int xe_prepare(xe_vm* vm) {
   void* jit = nullptr;
   bool jit_general = false;
   if (int rc = select_engine(vm, jit, jit_general)) return rc;
-  if (jit && keyed_candidate(vm)) keyed_kernel(vm, jit);
-  if (jit) lean_kernel(vm, jit);
+  if (jit && keyed_candidate(vm)) variant_kernel(vm, jit, kKeyedVariant);
+  if (jit) variant_kernel(vm, jit, kLeanVariant);
   return dsync(vm->stream) ? fail(vm, XE_ERR_DEVICE, "sync") : XE_OK;
 }
 
@@ -3748,13 +3891,13 @@ int xe_run_batch_device_async(xe_vm* vm, void* d_umem, uint64_t umem_len, const 
       words.push_back(m.vals_alloc / 8);
     }
   }
-  if (jit && !P.results && !P.regs) jit = lean_kernel(vm, jit);  // verdicts only: the lean variant
+  if (jit && !P.results && !P.regs) jit = variant_kernel(vm, jit, kLeanVariant);  // verdicts only: the lean variant
   const uint32_t grid = parallel_grid(vm, jit, general, n, P.nmaps);
   if (general && ensure_arena(vm, false, grid * 256, P.gen)) return fail(vm, XE_ERR_NOMEM, "device alloc (arena)");
   if (!src.empty() && launch_prologue(src.data(), dst.data(), words.data(), uint32_t(src.size()), nullptr, 0, s))
     return fail(vm, XE_ERR_DEVICE, "prologue");
   sl.t0.rec(s);
-  if ((jit ? launch_jit(jit, &P, grid, 256, s) : launch_interp(&P, grid, 256, s))) return fail(vm, XE_ERR_DEVICE, "kernel launch");
+  if (launch_emulator(jit, &P, grid, 256, s)) return fail(vm, XE_ERR_DEVICE, "kernel launch");
   sl.t1.rec(s);
   for (size_t i : big) {
     HostMap& m = vm->maps[i];

@@ -59,7 +59,7 @@ def test_ordered_program_falls_back(gpu_lib, oracle_lib, engine):
     b = run_one(oracle_lib, k["program"], k["maps"], umem, descs)
     assert_same(a, b, "ordered rmw")
     # one key written by every packet: a single chain holding the whole batch, which the staged
-    # one-lane replay runs faster than a chain lane (xe_runtime.cpp keyed: XE_KS_CLONG)
+    # one-lane replay runs faster than a chain lane (xe_runtime.cpp BatchRun::keyed_order: XE_KS_CLONG)
     assert a[0].stats["conflict"] == 1 and a[0].stats["mode_used"] == MODE_SEQUENTIAL
     # packet i saw counter value i: the exact sequential order
     assert (a[0].results["r0"] == np.arange(3000)).all()

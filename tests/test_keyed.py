@@ -1,4 +1,4 @@
-"""Keyed ordered execution (xe_internal.h XE_MODE_SPEC / XE_MODE_CHAIN; xe_runtime.cpp keyed).
+"""Keyed ordered execution (xe_internal.h XE_MODE_SPEC / XE_MODE_CHAIN; xe_runtime.cpp BatchRun::keyed).
 
 Programs that write map entries — an in-program insert (bpf_map_update_elem), a plain store into a map
 value, an ARRAY update — are order-dependent: the reference runs the packets one after another

@@ -39,7 +39,8 @@ def test_sanitized_oracle_and_hostsim_agree(tmp_path):
     hdrs = sorted(csrc.glob("*.h")) + [ROOT / "include" / "xdpemu.h", ROOT / "include" / "xdpemu_io.h"]
     orc = _build(OUT / "liboracle_san.so", [cxx, *FLAGS, "-fPIC", "-shared", str(ROOT / "oracle" / "oracle.cpp")],
                  [ROOT / "oracle" / "oracle.cpp", ROOT / "oracle" / "oracle.h", *hdrs])
-    sim_src = [csrc / "xe_runtime.cpp", csrc / "xe_io.cpp", csrc / "xe_multi.cpp", csrc / "xe_jit.cpp"]
+    from gobpfld_amd.build import HOSTSIM_UNITS
+    sim_src = [csrc / u for u in HOSTSIM_UNITS]
     sim = _build(OUT / "libxdpemu_hostsim_san.so",
                  [cxx, *FLAGS, "-fPIC", "-shared", "-DXE_HOSTSIM", "-DXE_HOSTSIM_POISON", *map(str, sim_src), "-pthread"], sim_src + hdrs)
     drv = _build(OUT / "san_driver", [cxx, *FLAGS, str(SAN / "san_driver.cpp"), "-ldl"], [SAN / "san_driver.cpp"])
