@@ -27,8 +27,19 @@ def test_dispatch_equals_numpy(hostsim_lib, n):
     DC.check_dispatch(hostsim_lib, False, n)
 
 
+@pytest.mark.parametrize("ver_offset", (1, 2, 3))
+@pytest.mark.parametrize("n", DC.UNALIGNED_SIZES)
+def test_dispatch_unaligned_verdicts(hostsim_lib, n, ver_offset):
+    DC.check_dispatch(hostsim_lib, False, n, names=("uniform", "failed10"), ver_offset=ver_offset)
+
+
 def test_dispatch_argument_errors(hostsim_lib):
     DC.check_errors(hostsim_lib, False)
+
+
+@pytest.mark.parametrize("room", DC.STRIDE_ROOMS)
+def test_gather_grid_stride(hostsim_lib, room):
+    DC.check_gather_stride(hostsim_lib, False, room)
 
 
 @pytest.mark.parametrize("room", DC.ROOMS)

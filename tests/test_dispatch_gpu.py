@@ -28,8 +28,19 @@ def test_dispatch_scan_loops(gpu_lib):
     DC.check_dispatch(gpu_lib, True, MANY_TILES, names=("uniform", "failed10"))
 
 
+@pytest.mark.parametrize("ver_offset", (1, 2, 3))
+@pytest.mark.parametrize("n", DC.UNALIGNED_SIZES)
+def test_dispatch_unaligned_verdicts(gpu_lib, n, ver_offset):
+    DC.check_dispatch(gpu_lib, True, n, names=("uniform", "failed10"), ver_offset=ver_offset)
+
+
 def test_dispatch_argument_errors(gpu_lib):
     DC.check_errors(gpu_lib, True)
+
+
+@pytest.mark.parametrize("room", DC.STRIDE_ROOMS)
+def test_gather_grid_stride(gpu_lib, room):
+    DC.check_gather_stride(gpu_lib, True, room)
 
 
 @pytest.mark.parametrize("room", DC.ROOMS)

@@ -13,7 +13,7 @@ def dev(a):
 
 
 def test_hash_restatement_guard(hostsim_lib):
-    for ks in MC.KEY_SIZES:
+    for ks in MC.GUARD_KEY_SIZES:
         MC.guard_hash_restatement(hostsim_lib, ks)
 
 
@@ -28,7 +28,35 @@ def test_array_matrix(hostsim_lib, oracle_lib, vs):
     MC.run_matrix(hostsim_lib, oracle_lib, dev, MAP_ARRAY, 4, vs)
 
 
-@pytest.mark.parametrize("ks", (8, 13, 64))
+@pytest.mark.parametrize("ks,vs", MC.EDGE_PAIRS)
+def test_hash_matrix_edges(hostsim_lib, oracle_lib, ks, vs):
+    MC.run_matrix(hostsim_lib, oracle_lib, dev, MAP_HASH, ks, vs, counts=MC.EDGE_COUNTS)
+
+
+@pytest.mark.parametrize("vs", MC.EDGE_VALUE_SIZES)
+def test_array_matrix_edges(hostsim_lib, oracle_lib, vs):
+    MC.run_matrix(hostsim_lib, oracle_lib, dev, MAP_ARRAY, 4, vs, counts=MC.EDGE_COUNTS)
+
+
+@pytest.mark.parametrize("ks,vs", MC.ALIGN_HASH)
+def test_hash_alignment(hostsim_lib, oracle_lib, ks, vs):
+    MC.run_alignment(hostsim_lib, oracle_lib, dev, MAP_HASH, ks, vs)
+
+
+@pytest.mark.parametrize("vs", MC.ALIGN_ARRAY)
+def test_array_alignment(hostsim_lib, oracle_lib, vs):
+    MC.run_alignment(hostsim_lib, oracle_lib, dev, MAP_ARRAY, 4, vs)
+
+
+def test_contention(hostsim_lib, oracle_lib):
+    MC.run_contention(hostsim_lib, oracle_lib, dev)
+
+
+def test_nil_backed_values(hostsim_lib, oracle_lib):
+    MC.run_vlen0(hostsim_lib, oracle_lib, dev)
+
+
+@pytest.mark.parametrize("ks", (8, 13, 24, 64))
 def test_probe_chains(hostsim_lib, oracle_lib, ks):
     MC.run_probe_chains(hostsim_lib, oracle_lib, dev, ks=ks)
 

@@ -33,7 +33,37 @@ def test_array_matrix(gpu_lib, oracle_lib, vs):
     MC.run_matrix(gpu_lib, oracle_lib, dev if vs in (1, 24) else staged, MAP_ARRAY, 4, vs)
 
 
-@pytest.mark.parametrize("ks", (8, 13, 64))
+@pytest.mark.parametrize("ks,vs", MC.EDGE_PAIRS)
+def test_hash_matrix_edges(gpu_lib, oracle_lib, ks, vs):
+    MC.run_matrix(gpu_lib, oracle_lib, dev if MC.EDGE_PAIRS.index((ks, vs)) % 2 == 0 else staged, MAP_HASH, ks, vs,
+                  counts=MC.EDGE_COUNTS)
+
+
+@pytest.mark.parametrize("vs", MC.EDGE_VALUE_SIZES)
+def test_array_matrix_edges(gpu_lib, oracle_lib, vs):
+    MC.run_matrix(gpu_lib, oracle_lib, staged if MC.EDGE_VALUE_SIZES.index(vs) % 2 == 0 else dev, MAP_ARRAY, 4, vs,
+                  counts=MC.EDGE_COUNTS)
+
+
+@pytest.mark.parametrize("ks,vs", MC.ALIGN_HASH)
+def test_hash_alignment(gpu_lib, oracle_lib, ks, vs):
+    MC.run_alignment(gpu_lib, oracle_lib, dev, MAP_HASH, ks, vs)
+
+
+@pytest.mark.parametrize("vs", MC.ALIGN_ARRAY)
+def test_array_alignment(gpu_lib, oracle_lib, vs):
+    MC.run_alignment(gpu_lib, oracle_lib, dev, MAP_ARRAY, 4, vs)
+
+
+def test_contention(gpu_lib, oracle_lib):
+    MC.run_contention(gpu_lib, oracle_lib, dev)
+
+
+def test_nil_backed_values(gpu_lib, oracle_lib):
+    MC.run_vlen0(gpu_lib, oracle_lib, dev)
+
+
+@pytest.mark.parametrize("ks", (8, 13, 24, 64))
 def test_probe_chains(gpu_lib, oracle_lib, ks):
     MC.run_probe_chains(gpu_lib, oracle_lib, dev, ks=ks)
 
