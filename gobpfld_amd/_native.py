@@ -68,6 +68,11 @@ class TraceRec(C.Structure):  # xe_trace_rec: one Step's VM.String (emulator/vm.
                 ("sf", C.c_uint32), ("kind", C.c_uint8 * 11), ("pad", C.c_uint8), ("val", C.c_int64 * 11)]
 
 
+class MapFilter(C.Structure):  # xe_map_filter
+    _fields_ = [("op", C.c_uint32), ("offset", C.c_uint32), ("width", C.c_uint32), ("pad", C.c_uint32),
+                ("operand", C.c_uint64)]
+
+
 # xe_helper_fn: int fn(void* user, uint32_t packet, const int64_t args[5], const uint8_t kinds[5], int64_t* r0)
 HELPER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8),
                         C.POINTER(C.c_int64))
@@ -152,6 +157,10 @@ _SIGS = {
     "map_lookup_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P]),
     "map_update_batch_staged": (C.c_int, [P, C.c_int32, P, P, C.c_uint64]),
     "map_delete_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P]),
+    "map_scan_device": (C.c_int, [P, C.c_int32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
+    "map_expire_device": (C.c_int, [P, C.c_int32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
+    "map_scan": (C.c_int, [P, C.c_int32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "map_expire": (C.c_int, [P, C.c_int32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "debug_map_traffic": (C.c_int, [P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "multi_create": (C.c_int, [P, C.c_uint32, C.POINTER(P)]),
     "multi_destroy": (None, [P]),
@@ -184,6 +193,7 @@ HEADER_SYMBOLS = [
     "xe_debug_set_lru_epoch", "xe_debug_map_pool",
     "xe_map_lookup_batch_device", "xe_map_update_batch_device", "xe_map_delete_batch_device",
     "xe_map_lookup_batch", "xe_map_update_batch_staged", "xe_map_delete_batch", "xe_debug_map_traffic",
+    "xe_map_scan_device", "xe_map_expire_device", "xe_map_scan", "xe_map_expire",
     "xe_set_kernel_cache", "xe_kernel_source", "xe_compile_kernel_source", "xe_kernel_object_name",
     "xe_kernel_cache_stats",
     "xe_cancel", "xe_trace_config", "xe_trace_read", "xe_set_helper", "xe_reset_helper",

@@ -1,5 +1,6 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
-// xe_map_update_batch_device, xe_map_delete_batch_device): the per-key decision logic that the kernels
+// xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device): the
+// per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
 // declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
 //
@@ -25,6 +26,20 @@
 //            CLAIM   one CAS FULL -> TOMB | (i+1) << 32 per present key: one entry per distinct key wins
 //            ZERO    the winner's sub-group zeroes the value (map and delta base), the record becomes a
 //                    plain tombstone and the count drops
+//   scan /   SELECT  one slot per lane over tiles of kMsTile consecutive slots (HASH: table slots; ARRAY:
+//   expire           indices), one wave per tile in kMsRounds rounds: a FULL record's field is assembled from
+//                    its value bytes and the filter evaluated, once; one 64-bit ballot per round goes to a
+//                    bitmap, one match count per tile to the tile counts
+//            SCAN    one workgroup turns the tile counts into their exclusive sums, kMsScanPass counts a
+//                    pass with a carry; the total lands in the counters (kMoMatched) and the host reads it
+//            SCATTER reads the bitmap and the tile bases only: a set bit's rank is its tile's base + the
+//                    bits of the rounds before + the bits of the lanes before; rank < r: slot[rank] = slot.
+//                    Ascending slot order, a function of the map's state alone
+//            COPY    a sub-group per selected entry: its key (HASH: the record's key words; ARRAY: the
+//                    index) and its value (zeros under VLEN0) to entry j of the outputs
+//            EXPIRE  (expire only, after COPY) the same sub-groups leave their records as DELETE ZERO
+//                    leaves one: value zeroed in the map and the delta base, a plain tombstone with its
+//                    key words kept; the count drops by r
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
 // an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
@@ -47,6 +62,7 @@ enum : uint32_t {
   XE_MO_LOOKUP_FIND = 0, XE_MO_LOOKUP_VALUE,
   XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY,
   XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO,
+  XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN, XE_MO_SCAN_SCATTER, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE,
   XE_MO_STEPS
 };
 
@@ -56,8 +72,13 @@ constexpr uint32_t kMoVlen0 = 0x40000000u;   // slot[i]: the record's value read
 constexpr uint32_t kMoSlotMask = 0x3fffffffu;  // (cap <= 2^27, ARRAY indices are checked against it)
 constexpr uint32_t kMoAbsent = kMoSlotMask;
 // counters of a batch (u32 words of the scratch)
-constexpr uint32_t kMoNew = 0, kMoErr = 1, kMoGone = 2, kMoCounters = 16;
+constexpr uint32_t kMoNew = 0, kMoErr = 1, kMoGone = 2, kMoMatched = 3, kMoCounters = 16;
 constexpr uint32_t kMoErrRange = 1, kMoErrFull = 2;  // an ARRAY index out of range; no free record in the table
+// scan / expire: a tile is kMsTile consecutive slots, one wave's work in kMsRounds rounds of 64; the SCAN
+// step sums kMsScanPass tile counts a pass (262,144 slots: a table of 2^20 slots takes four passes)
+constexpr uint32_t kMsRounds = 4, kMsTile = 64 * kMsRounds, kMsScanThreads = 256, kMsScanPass = kMsScanThreads * 4;
+// the filter's ops (include/xdpemu.h XE_MF_*)
+enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
 
 struct XeMapOp {
   uint32_t kind;  // XE_DM_ARRAY / XE_DM_HASH
@@ -74,7 +95,15 @@ struct XeMapOp {
   uint8_t* found;         // may be null
   uint32_t* slot;         // [n] scratch
   uint32_t* ctr;          // [kMoCounters] scratch, zero at the batch's start
+  // scan / expire (n is then r, the entries reported)
+  uint32_t f_op, f_off, f_width;  // the filter: kMf*, the field's byte offset in the value and its width
+  uint32_t nslots, sbase;         // the slots looked at: sbase .. sbase + nslots (the empty key: the record past the table)
+  uint64_t f_operand;
+  uint64_t* bitmap;       // [tiles x kMsRounds] one bit per slot: selected
+  uint32_t* tile;         // [tiles] matches per tile (SELECT), then the matches in front of the tile (SCAN)
+  uint8_t* keys_out;      // may be null (so may values_out)
 };
+inline uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
 
 // lanes that share one value (a power of two <= 64)
 inline uint32_t xe_mo_lanes(uint32_t value_size) {
@@ -343,12 +372,126 @@ XE_HD void mo_delete_zero_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint3
   if (sub == 0) o.recs[uint64_t(s) * o.rwords] = XE_SLOT_TOMB;  // a plain tombstone, its key words kept
 }
 
+// ---------------------------------------------------------------- scan / expire
+XE_HD bool ms_filter(uint32_t op, uint64_t field, uint64_t operand) {
+  switch (op) {
+    case kMfAll: return true;
+    case kMfEq: return field == operand;
+    case kMfNe: return field != operand;
+    case kMfLt: return field < operand;
+    case kMfLe: return field <= operand;
+    case kMfGt: return field > operand;
+    case kMfGe: return field >= operand;
+    case kMfAnyBits: return (field & operand) != 0;
+    case kMfNoBits: return (field & operand) == 0;
+    default: return false;
+  }
+}
+// The field of the value at v, little endian, zero-extended: one load where the address allows it.
+XE_HD uint64_t ms_field(const uint8_t* v, uint32_t width) {
+  if (!(uintptr_t(v) & (width - 1))) {
+    if (width == 8) return *reinterpret_cast<const uint64_t*>(v);
+    if (width == 4) return *reinterpret_cast<const uint32_t*>(v);
+    if (width == 2) return *reinterpret_cast<const uint16_t*>(v);
+    return *v;
+  }
+  uint64_t f = 0;
+  for (uint32_t b = 0; b < 8; b++)
+    if (b < width) f |= uint64_t(v[b]) << (8 * b);
+  return f;
+}
+// Is slot sbase + s (s < nslots) selected? HASH: FULL records only (a tombstone keeps key words and a zero
+// value and never matches); a nil-backed value reads as zeros, as it does for xe_map_lookup.
+XE_HD bool ms_select_item(const XeMapOp& o, uint32_t s) {
+  const uint32_t at = o.sbase + s;
+  bool zero = false;
+  if (o.kind == XE_DM_HASH) {
+    const uint32_t st = uint32_t(o.recs[uint64_t(at) * o.rwords]);
+    if (!(st & XE_SLOT_FULL)) return false;
+    zero = (st & XE_SLOT_VLEN0) != 0;
+  }
+  if (o.f_op == kMfAll) return true;
+  return ms_filter(o.f_op, zero ? 0 : ms_field(o.vals + uint64_t(at) * o.value_size + o.f_off, o.f_width), o.f_operand);
+}
+// Lane `lane` of round `round` of tile t, given the round's bitmap word and the matches in front of the
+// round: a selected slot's rank; below n it is reported.
+XE_HD void ms_scatter_item(const XeMapOp& o, uint32_t t, uint32_t round, uint32_t lane, uint64_t word, uint32_t before) {
+  if (!((word >> lane) & 1)) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t rank = before + __builtin_amdgcn_mbcnt_hi(uint32_t(word >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(word), 0));
+#else
+  const uint32_t rank = before + uint32_t(__builtin_popcountll(word & ((uint64_t(1) << lane) - 1)));
+#endif
+  if (rank < o.n) o.slot[rank] = o.sbase + t * kMsTile + round * 64 + lane;
+}
+XE_HD void ms_copy_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t lanes) {
+  const uint32_t s = o.slot[j];
+  if (o.keys_out) {
+    if (o.kind == XE_DM_ARRAY) {
+      uint8_t* k = o.keys_out + uint64_t(j) * 4;
+      if (sub == 0) k[0] = uint8_t(s), k[1] = uint8_t(s >> 8), k[2] = uint8_t(s >> 16), k[3] = uint8_t(s >> 24);
+    } else if (o.key_size) {
+      mo_move(o.keys_out + uint64_t(j) * o.key_size, reinterpret_cast<const uint8_t*>(o.recs + uint64_t(s) * o.rwords + 1),
+              o.key_size, sub, lanes);
+    }
+  }
+  if (o.values_out) {
+    const bool zero = o.kind == XE_DM_HASH && (uint32_t(o.recs[uint64_t(s) * o.rwords]) & XE_SLOT_VLEN0);
+    mo_move(o.values_out + uint64_t(j) * o.value_size, zero ? nullptr : o.vals + uint64_t(s) * o.value_size, o.value_size, sub, lanes);
+  }
+}
+XE_HD void ms_expire_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t lanes) {
+  if (j == 0 && sub == 0) *o.count -= o.n;
+  const uint32_t s = o.slot[j];
+  mo_move(o.vals + uint64_t(s) * o.value_size, nullptr, o.value_size, sub, lanes);
+  mo_move(o.snap + uint64_t(s) * o.value_size, nullptr, o.value_size, sub, lanes);
+  if (sub == 0) o.recs[uint64_t(s) * o.rwords] = XE_SLOT_TOMB;  // a plain tombstone, its key words kept
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
 // The host simulation: the same items, one after another.
 static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
   const XeMapOp& o = *op;
+  const uint32_t tiles = xe_ms_tiles(o.nslots);
+  if (step == XE_MO_SCAN_SELECT) {
+    for (uint32_t t = 0; t < tiles; t++) {
+      uint32_t cnt = 0;
+      for (uint32_t r = 0; r < kMsRounds; r++) {
+        uint64_t word = 0;
+        for (uint32_t lane = 0; lane < 64; lane++) {
+          const uint32_t s = t * kMsTile + r * 64 + lane;
+          if (s < o.nslots && ms_select_item(o, s)) word |= uint64_t(1) << lane;
+        }
+        o.bitmap[uint64_t(t) * kMsRounds + r] = word;
+        cnt += uint32_t(__builtin_popcountll(word));
+      }
+      o.tile[t] = cnt;
+    }
+    return 0;
+  }
+  if (step == XE_MO_SCAN_SCAN) {
+    uint32_t carry = 0;
+    for (uint32_t t = 0; t < tiles; t++) {
+      const uint32_t c = o.tile[t];
+      o.tile[t] = carry;
+      carry += c;
+    }
+    o.ctr[kMoMatched] = carry;
+    return 0;
+  }
+  if (step == XE_MO_SCAN_SCATTER) {
+    for (uint32_t t = 0; t < tiles; t++) {
+      uint32_t before = o.tile[t];
+      for (uint32_t r = 0; r < kMsRounds; r++) {
+        const uint64_t word = o.bitmap[uint64_t(t) * kMsRounds + r];
+        for (uint32_t lane = 0; lane < 64; lane++) ms_scatter_item(o, t, r, lane, word, before);
+        before += uint32_t(__builtin_popcountll(word));
+      }
+    }
+    return 0;
+  }
   for (uint32_t i = 0; i < o.n; i++) {
     switch (step) {
       case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i), true); break;
@@ -360,6 +503,8 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
       case XE_MO_DELETE_FIND: mo_find_finish(o, i, mo_slot_of(o, i), false); break;
       case XE_MO_DELETE_CLAIM: mo_delete_claim_item(o, i); break;
       case XE_MO_DELETE_ZERO: mo_delete_zero_item(o, i, 0, 1); break;
+      case XE_MO_SCAN_COPY: ms_copy_item(o, i, 0, 1); break;
+      case XE_MO_SCAN_EXPIRE: ms_expire_item(o, i, 0, 1); break;
       default: return -1;
     }
   }

@@ -1,7 +1,8 @@
 // Device-resident batched map lookup, update and delete (xe_mapops.h: the steps and what each one
 // decides). One kernel per step; a step works either one batch entry per lane (probes, claims, marks) or
 // one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
-// destination allow it).
+// destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
+// one-workgroup prefix sum of the tile counts (SCAN); their COPY and EXPIRE are value kernels.
 //
 // 256-thread workgroups. Up to kMoOneTurn of them take one entry (or one sub-group's entry) per lane:
 // 65,536 keys in a lane step. A larger batch gets a quarter of the workgroups it would need for that, at
@@ -108,17 +109,117 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_value_kernel(XeMapOp o, u
       case XE_MO_LOOKUP_VALUE: mo_lookup_value_item(o, uint32_t(i), sub, LANES); break;
       case XE_MO_UPDATE_COPY: mo_update_copy_item(o, uint32_t(i), sub, LANES); break;
       case XE_MO_DELETE_ZERO: mo_delete_zero_item(o, uint32_t(i), sub, LANES); break;
+      case XE_MO_SCAN_COPY: ms_copy_item(o, uint32_t(i), sub, LANES); break;
+      case XE_MO_SCAN_EXPIRE: ms_expire_item(o, uint32_t(i), sub, LANES); break;
       default: break;
+    }
+  }
+}
+
+// ---- scan / expire. SELECT and SCATTER: one wave per tile of kMsTile consecutive slots, kMsRounds rounds
+// of one slot per lane; the waves stride over the tiles. A wave's round reads word 0 of 64 consecutive
+// records (512 to 4,096 contiguous bytes) and, for the FULL ones, the field's bytes of 64 consecutive
+// values; the rounds are independent, so their loads are in flight together.
+__global__ void __launch_bounds__(kMoThreads) xe_mapscan_select_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    bool hit[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      hit[r] = s < o.nslots && ms_select_item(o, s);
+    }
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const unsigned long long b = __ballot(hit[r]);
+      if (lane == 0) o.bitmap[uint64_t(t) * kMsRounds + r] = b;
+      cnt += uint32_t(__popcll(b));
+    }
+    if (lane == 0) o.tile[t] = cnt;
+  }
+}
+
+// Exclusive sums of the tile counts in place, by one workgroup: four counts per lane, an inclusive scan
+// across each wave, the waves' sums through LDS, a carry from pass to pass.
+__global__ void __launch_bounds__(kMsScanThreads) xe_mapscan_scan_kernel(XeMapOp o, uint32_t tiles) {
+  constexpr uint32_t kWaves = kMsScanThreads / 64;
+  __shared__ uint32_t wsum[kWaves];
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < tiles; base += kMsScanPass) {
+    const uint32_t at = base + t * 4;
+    uint32_t x[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) x[j] = at + j < tiles ? o.tile[at + j] : 0;
+    uint32_t inc = x[0] + x[1] + x[2] + x[3];
+    const uint32_t sum = inc;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const uint32_t y = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += y;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t before = carry, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kWaves; k++) {
+      const uint32_t s = wsum[k];
+      before += k < w ? s : 0;
+      all += s;
+    }
+    uint32_t e = before + inc - sum;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+      if (at + j < tiles) o.tile[at + j] = e;
+      e += x[j];
+    }
+    carry += all;
+    __syncthreads();  // (wsum is written again in the next pass)
+  }
+  if (t == 0) o.ctr[kMoMatched] = carry;
+}
+
+__global__ void __launch_bounds__(kMoThreads) xe_mapscan_scatter_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint32_t before = o.tile[t];
+    if (before >= o.n) continue;  // every entry to report lies in front of this tile
+    uint64_t word[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap[uint64_t(t) * kMsRounds + r];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      ms_scatter_item(o, t, r, lane, word[r], before);
+      before += uint32_t(__popcll(word[r]));
     }
   }
 }
 
 }  // namespace
 
+// SELECT / SCATTER: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
+// would take, between kMoOneTurn and kMoMaxBlocks (the file's policy), the waves striding over the tiles.
+static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
+  const uint32_t tiles = xe_ms_tiles(op->nslots);
+  if (!tiles) return 0;
+  if (step == XE_MO_SCAN_SCAN) {
+    hipLaunchKernelGGL(xe_mapscan_scan_kernel, dim3(1), dim3(kMsScanThreads), 0, s, *op, tiles);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  const uint32_t want = (tiles + kMoThreads / 64 - 1) / (kMoThreads / 64);
+  const uint32_t blocks = want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks;
+  if (step == XE_MO_SCAN_SELECT) hipLaunchKernelGGL(xe_mapscan_select_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else hipLaunchKernelGGL(xe_mapscan_scatter_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream) {
-  if (!op->n) return 0;
   hipStream_t s = hipStream_t(stream);
-  const bool value = step == XE_MO_LOOKUP_VALUE || step == XE_MO_UPDATE_COPY || step == XE_MO_DELETE_ZERO;
+  if (step == XE_MO_SCAN_SELECT || step == XE_MO_SCAN_SCAN || step == XE_MO_SCAN_SCATTER) return launch_mapscan(op, step, s);
+  if (!op->n) return 0;
+  const bool value = step == XE_MO_LOOKUP_VALUE || step == XE_MO_UPDATE_COPY || step == XE_MO_DELETE_ZERO ||
+                     step == XE_MO_SCAN_COPY || step == XE_MO_SCAN_EXPIRE;
   const uint32_t lanes = value ? xe_mo_lanes(op->value_size) : 1, per = kMoThreads / lanes;
   const uint64_t want = (uint64_t(op->n) + per - 1) / per;
   const uint64_t blocks = want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks;

@@ -974,6 +974,7 @@ struct xe_vm {
   void* d_mo_keys = nullptr; size_t d_mo_keys_cap = 0;
   void* d_mo_vals = nullptr; size_t d_mo_vals_cap = 0;
   void* d_mo_found = nullptr; size_t d_mo_found_cap = 0;
+  void* d_ms = nullptr; size_t d_ms_cap = 0;  // scan / expire: the table's bitmap and the tile counts
 };
 // ---- keyed ordered execution buffers (XeKeyed), sized for n packets
 static void keyed_free(xe_vm* vm) {
@@ -1719,7 +1720,7 @@ void xe_destroy(xe_vm* vm) {
   dev_free(vm->d_arena_par); dev_free(vm->d_arena_seq); dev_free(vm->d_ksnap);
   dev_free(vm->d_umem); dev_free(vm->d_desc); dev_free(vm->d_res); dev_free(vm->d_ver); dev_free(vm->d_regs);
   dev_free(vm->d_usnap); dev_free(vm->d_ovl); dev_free(vm->d_app); dev_free(vm->d_app_sort); dev_free(vm->d_relink);
-  dev_free(vm->d_mo); dev_free(vm->d_mo_keys); dev_free(vm->d_mo_vals); dev_free(vm->d_mo_found);
+  dev_free(vm->d_mo); dev_free(vm->d_mo_keys); dev_free(vm->d_mo_vals); dev_free(vm->d_mo_found); dev_free(vm->d_ms);
   keyed_free(vm);
   vm->t0.fini(); vm->t1.fini(); vm->t2.fini();
 #ifndef XE_HOSTSIM
@@ -4287,8 +4288,9 @@ int xe_map_state_import(xe_vm* vm, int32_t mi, const void* d_in, void* stream) {
 namespace {
 constexpr uint64_t kMoMaxCount = 1ull << 31;
 
-// Common start of the three calls: pipelined batches complete, the map is of a served kind and current on
-// the device, the per-entry scratch holds `count` slots behind zeroed counters. 1: nothing to do (count 0).
+// Common start of the batched calls and of scan / expire: pipelined batches complete, the map is of a served
+// kind and current on the device, the per-entry scratch holds `count` slots behind zeroed counters. 1: nothing
+// to do (count 0).
 int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, HostMap** mp, XeMapOp* op, xe_stream_t* sp) {
   if (!vm) return XE_ERR_INVAL;
   if (int rc = xe_sync(vm)) return rc;
@@ -4467,6 +4469,89 @@ int xe_map_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count,
   if (found && (d2h(found, vm->d_mo_found, size_t(count), vm->stream) || dsync(vm->stream)))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
   return XE_OK;
+}
+
+// Scan and expire (xe_mapops.h SELECT .. EXPIRE). host: keys / values are host memory, staged through
+// d_mo_keys / d_mo_vals once r is known. The per-entry scratch and the staging hold r entries, never
+// cap_entries or the table.
+static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
+                        uint64_t* matched, void* stream, bool expire, bool host) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const int rc = mapop_begin(vm, mi, 1, expire, host ? nullptr : stream, &m, &o, &s);  // (the counters; slots come with r)
+  if (rc < 0) return rc;
+  if (expire && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  const xe_map_filter all{};  // XE_MF_ALL
+  if (!f) f = &all;
+  if (f->op >= kMfOps) return fail(vm, XE_ERR_INVAL, "map filter: unknown op");
+  if (f->pad) return fail(vm, XE_ERR_INVAL, "map filter: pad must be 0");
+  if (f->op != XE_MF_ALL) {
+    if (f->width != 1 && f->width != 2 && f->width != 4 && f->width != 8) return fail(vm, XE_ERR_INVAL, "map filter: width must be 1, 2, 4 or 8");
+    if (uint64_t(f->offset) + f->width > m->def.value_size) return fail(vm, XE_ERR_INVAL, "map filter: the field lies outside the value");
+    o.f_off = f->offset;
+    o.f_width = f->width;
+    o.f_operand = f->operand;
+  }
+  o.f_op = f->op;
+  if (m->dkind == XE_DM_ARRAY) o.nslots = m->def.max_entries;
+  else if (m->def.key_size == 0) o.sbase = m->cap, o.nslots = 1;  // the empty key: the one record past the table
+  else o.nslots = m->cap;
+  *matched = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return XE_OK;
+  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
+  o.bitmap = (uint64_t*)vm->d_ms;
+  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds);
+  if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
+  uint32_t total = 0;
+  if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map scan");
+  *matched = total;
+  const uint32_t r = uint32_t(std::min<uint64_t>(total, cap_entries));
+  const bool out = keys || values;
+  if (!r || (!expire && !out)) return XE_OK;
+  const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size;
+  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  o.ctr = (uint32_t*)vm->d_mo;
+  o.slot = o.ctr + kMoCounters;
+  o.n = r;
+  if (host && ((keys && ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb)) || (values && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb))))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  o.keys_out = (uint8_t*)(!keys ? nullptr : host ? vm->d_mo_keys : keys);
+  o.values_out = (uint8_t*)(!values ? nullptr : host ? vm->d_mo_vals : values);
+  if (int e = mapop_steps(vm, o, {XE_MO_SCAN_SCATTER}, s)) return e;
+  if (out)
+    if (int e = mapop_steps(vm, o, {XE_MO_SCAN_COPY}, s)) return e;
+  uint32_t cnt = 0;
+  if (expire) {
+    if (int e = mapop_steps(vm, o, {XE_MO_SCAN_EXPIRE}, s)) return e;
+    if (d2h(&cnt, m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, "map expire");
+  }
+  if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s))))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, expire ? "map expire" : "map scan");
+  if (expire) {
+    m->live = cnt;
+    m->dev_dirty = true;
+    vm->staged_slot = -1;
+  }
+  return XE_OK;
+}
+
+int xe_map_scan_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* d_keys, void* d_values, uint64_t cap_entries,
+                       uint64_t* matched, void* stream) {
+  return map_scan_run(vm, mi, f, d_keys, d_values, cap_entries, matched, stream, false, false);
+}
+int xe_map_expire_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* d_keys, void* d_values, uint64_t cap_entries,
+                         uint64_t* matched, void* stream) {
+  return map_scan_run(vm, mi, f, d_keys, d_values, cap_entries, matched, stream, true, false);
+}
+int xe_map_scan(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries, uint64_t* matched) {
+  return map_scan_run(vm, mi, f, keys, values, cap_entries, matched, nullptr, false, true);
+}
+int xe_map_expire(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries, uint64_t* matched) {
+  return map_scan_run(vm, mi, f, keys, values, cap_entries, matched, nullptr, true, true);
 }
 
 int xe_debug_map_traffic(xe_vm* vm, int32_t mi, uint64_t* uploads, uint64_t* downloads) {

@@ -48,6 +48,19 @@ class MapDef:
     flags: int = 0
 
 
+MF_ALL, MF_EQ, MF_NE, MF_LT, MF_LE, MF_GT, MF_GE, MF_ANYBITS, MF_NOBITS = range(9)  # XE_MF_* (include/xdpemu.h)
+
+
+@dataclass
+class MapFilter:
+    """xe_map_filter: `op` applied to the unsigned little-endian field of `width` bytes at byte `offset`
+    of the value, against `operand` (VM.map_scan / VM.map_expire)."""
+    op: int = MF_ALL
+    offset: int = 0
+    width: int = 8
+    operand: int = 0
+
+
 @dataclass
 class Settings:
     max_steps: int = 1 << 20
@@ -322,6 +335,47 @@ class VM:
             rc = self.lib.map_delete_batch(self.h, m, k.ctypes.data, n, found.ctypes.data)
         self._check(rc, "map delete batch")
         return found
+
+    # ---- scan and expire on the device copy (ARRAY / HASH; xe_map_scan_device / xe_map_expire_device)
+    def _map_scan(self, m: int, flt, cap, on_device: bool, expire: bool):
+        d = self.map_defs[m]
+        ks = 4 if d.type in ARRAY_TYPES else d.key_size
+        what = "map expire" if expire else "map scan"
+        dev_fn = self.lib.map_expire_device if expire else self.lib.map_scan_device
+        host_fn = self.lib.map_expire if expire else self.lib.map_scan
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        fp = None if cf is None else C.byref(cf)
+        n = C.c_uint64(0)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.settings.device)
+            # the calls run on the VM's stream: whatever torch has queued on its own completes first
+            torch.cuda.current_stream(dev).synchronize()
+        if cap is None:  # count first, then fetch all
+            self._check(self.lib.map_scan_device(self.h, m, fp, None, None, 0, C.byref(n), None), what)
+            cap = n.value
+        if on_device:
+            # (the call writes the r entries it reports; the rest is cut off below)
+            keys = torch.empty((cap, ks), dtype=torch.uint8, device=dev)
+            vals = torch.empty((cap, d.value_size), dtype=torch.uint8, device=dev)
+            rc = dev_fn(self.h, m, fp, keys.data_ptr() or None, vals.data_ptr() or None, cap, C.byref(n), None)
+        else:
+            keys = np.zeros((cap, ks), dtype=np.uint8)
+            vals = np.zeros((cap, d.value_size), dtype=np.uint8)
+            rc = host_fn(self.h, m, fp, keys.ctypes.data if cap else None, vals.ctypes.data if cap else None, cap, C.byref(n))
+        self._check(rc, what)
+        r = min(int(n.value), cap)
+        return keys[:r], vals[:r], int(n.value)
+
+    def map_scan(self, m: int, flt: "MapFilter | None" = None, cap: int | None = None, on_device: bool = False):
+        """(keys[r, key_size], values[r, value_size], matched): the entries of the device copy that satisfy
+        `flt` (None: all of them), in ascending slot order; r = min(matched, cap). cap None: count first,
+        then fetch them all. on_device: CUDA tensors instead of numpy arrays. ARRAY keys are u32 indices."""
+        return self._map_scan(m, flt, cap, on_device, False)
+
+    def map_expire(self, m: int, flt: "MapFilter | None" = None, cap: int | None = None, on_device: bool = False):
+        """map_scan that also removes the r entries it returns (HASH; xe_map_expire_device)."""
+        return self._map_scan(m, flt, cap, on_device, True)
 
     def map_traffic(self, m: int) -> tuple[int, int]:
         """xe_debug_map_traffic: (uploads, downloads) of the whole map so far."""

@@ -384,6 +384,62 @@ int xe_map_lookup_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t c
 int xe_map_update_batch_staged(xe_vm* vm, int32_t map_idx, const void* keys, const void* values, uint64_t count);
 int xe_map_delete_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t count, uint8_t* found);
 
+/* --- scan and expire on the device copy (ARRAY and HASH kinds): which entries are in the map, which of
+ * them satisfy a filter on one field of the value, and (expire) their removal, by kernels that read the
+ * slot table once at device bandwidth. Nothing of the map crosses to the host or back, where xe_map_dump /
+ * xe_map_count download the whole map first. The rules of the batched calls above hold: pipelined batches
+ * complete first (xe_sync), a map changed through the host calls is uploaded once, the call is finished
+ * when it returns, stream NULL is the VM's stream, every d_* is a device address (a host address in the
+ * host-simulation build); LRU_HASH, QUEUE, STACK and PERF_EVENT_ARRAY maps return XE_ERR_UNSUPPORTED.
+ *
+ *   entries: HASH kinds: the entries of the device table. ARRAY kinds: every index below max_entries,
+ *            its key the index as a u32. A HASH value whose backing became nil reads as zeros, for the
+ *            filter and in the output, as it does for xe_map_lookup. Deleted entries never match.
+ *   filter:  NULL or op XE_MF_ALL selects every entry (offset, width and operand are then ignored).
+ *            Otherwise the field is the `width` bytes (1, 2, 4 or 8) at byte `offset` of the value, any
+ *            alignment, little endian, zero-extended to 64 bits and compared unsigned with `operand`; an
+ *            operand wider than the field is no error, it simply never equals the field. An unknown op,
+ *            pad != 0, another width, or a field that does not lie inside value_size: XE_ERR_INVAL.
+ *   order:   ascending slot order (HASH: the table slot; ARRAY: the index): a function of the map's state
+ *            alone, so two scans of one state give identical bytes.
+ *   output:  *matched = the number of matching entries, always the total (NULL: XE_ERR_INVAL). With r =
+ *            min(*matched, cap_entries), entries 0 .. r-1 of that order go to d_keys (r x key_size bytes;
+ *            ARRAY: r x 4) and d_values (r x value_size), back to back; no byte past entry r is written.
+ *            Either pointer may be NULL and that array is not written. A caller that sees *matched >
+ *            cap_entries calls again with more room. cap_entries 0, or both pointers NULL on a scan,
+ *            only counts: a device-side xe_map_count, with or without a filter.
+ *   expire:  HASH kinds only (ARRAY: XE_ERR_INVAL, as xe_map_delete). Removes exactly the r entries it
+ *            reports, the first r matches of the order; the values written out are those before the
+ *            removal. With both pointers NULL it removes up to cap_entries matches silently. Each removed
+ *            entry is left as xe_map_delete_batch_device leaves one (a later insert of the same key takes
+ *            its record again), and like it the call writes the delta base of xe_map_delta and is refused
+ *            with XE_ERR_INVAL while a shard epoch is open. Scan changes no state and is allowed there. */
+#define XE_MF_ALL 0      /* every entry */
+#define XE_MF_EQ 1       /* field == operand */
+#define XE_MF_NE 2
+#define XE_MF_LT 3       /* unsigned compares of the zero-extended field with the u64 operand */
+#define XE_MF_LE 4
+#define XE_MF_GT 5
+#define XE_MF_GE 6
+#define XE_MF_ANYBITS 7  /* (field & operand) != 0 */
+#define XE_MF_NOBITS 8   /* (field & operand) == 0 */
+typedef struct xe_map_filter {
+  uint32_t op;      /* XE_MF_* */
+  uint32_t offset;  /* byte offset of the field inside the value; any alignment */
+  uint32_t width;   /* 1, 2, 4 or 8 bytes, little endian, unsigned */
+  uint32_t pad;     /* 0 */
+  uint64_t operand;
+} xe_map_filter;
+int xe_map_scan_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* d_keys, void* d_values,
+                       uint64_t cap_entries, uint64_t* matched, void* stream);
+int xe_map_expire_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* d_keys, void* d_values,
+                         uint64_t cap_entries, uint64_t* matched, void* stream);
+/* The same with host pointers: the r reported entries are staged through device buffers of the VM. */
+int xe_map_scan(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
+                uint64_t* matched);
+int xe_map_expire(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
+                  uint64_t* matched);
+
 /* --- one process, N devices (SURVEY §8b xe_run_batch_multi): the Go host shards a batch over the
  * GPUs of a node through the FFI alone. vms[k] runs on its own device with identical programs, maps
  * and map contents (the caller sets each up the same way). Exchange over RCCL (xGMI) when the devices
