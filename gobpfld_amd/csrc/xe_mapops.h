@@ -1,6 +1,6 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
-// xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device): the
-// per-key and per-slot decision logic that the kernels
+// xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device,
+// xe_map_top_device, xe_map_evict_device, xe_map_stats): the per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
 // declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
 //
@@ -40,6 +40,25 @@
 //            EXPIRE  (expire only, after COPY) the same sub-groups leave their records as DELETE ZERO
 //                    leaves one: value zeroed in the map and the delta base, a plain tombstone with its
 //                    key words kept; the count drops by r
+//   top /    PREFIX  the SELECT shape, one pass per byte of the order field, most significant first: a lane
+//   evict            evaluates the filter and reads the order field once; the rank key is the field, or its
+//                    complement within the width when the largest ranks first, so the smallest key always
+//                    ranks first. Keys that share the prefix fixed so far add to a 256-bin histogram of
+//                    their next byte (LDS per workgroup, one atomic per non-empty bin to the global bins)
+//            PICK    one workgroup: the bin in which the number still needed runs out is the next prefix
+//                    byte, the bins in front of it lower that number, the bins are cleared. Pass 0's bins sum
+//                    to the eligible entries (kMtMatched); the number needed starts as min(k, that). The
+//                    state lives in the counters: no host readback between the passes
+//            CUT     one more tile pass, two bitmaps with a count per tile each: key < cut ("beyond") and
+//                    key == cut ("equal"); nothing at all when nothing is needed
+//            SCAN    (the scan's, over the equal counts)
+//            TRIM    an equal bit's rank among the equals is its tile's base + the bits of the rounds before
+//                    + the bits of the lanes before, SCATTER's arithmetic; rank < the number still needed:
+//                    the bit joins the first bitmap and its tile's count. Ties are so taken in slot order
+//            SCAN, SCATTER, COPY, EXPIRE   unchanged: the first bitmap now holds exactly the r selected
+//   stats    STATS   one tile pass: count, sum, min and max of the field per lane, reduced across the wave and
+//                    the workgroup, one 64-bit atomic each per workgroup (integers: the order of arrival
+//                    does not matter)
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
 // an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
@@ -63,6 +82,7 @@ enum : uint32_t {
   XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY,
   XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO,
   XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN, XE_MO_SCAN_SCATTER, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE,
+  XE_MO_TOP_PREFIX, XE_MO_TOP_PICK, XE_MO_TOP_CUT, XE_MO_TOP_TRIM, XE_MO_TOP_STATS,
   XE_MO_STEPS
 };
 
@@ -73,6 +93,9 @@ constexpr uint32_t kMoSlotMask = 0x3fffffffu;  // (cap <= 2^27, ARRAY indices ar
 constexpr uint32_t kMoAbsent = kMoSlotMask;
 // counters of a batch (u32 words of the scratch)
 constexpr uint32_t kMoNew = 0, kMoErr = 1, kMoGone = 2, kMoMatched = 3, kMoCounters = 16;
+// top / evict: the eligible entries, the number still needed, the rank-key prefix fixed so far (two words);
+// stats: four 64-bit words (count, sum, ~min, max) from word kMtStats on
+constexpr uint32_t kMtMatched = 4, kMtNeed = 5, kMtPrefix = 6, kMtStats = 8, kMtBins = 256;
 constexpr uint32_t kMoErrRange = 1, kMoErrFull = 2;  // an ARRAY index out of range; no free record in the table
 // scan / expire: a tile is kMsTile consecutive slots, one wave's work in kMsRounds rounds of 64; the SCAN
 // step sums kMsScanPass tile counts a pass (262,144 slots: a table of 2^20 slots takes four passes)
@@ -102,6 +125,12 @@ struct XeMapOp {
   uint64_t* bitmap;       // [tiles x kMsRounds] one bit per slot: selected
   uint32_t* tile;         // [tiles] matches per tile (SELECT), then the matches in front of the tile (SCAN)
   uint8_t* keys_out;      // may be null (so may values_out)
+  // top / evict / stats
+  uint32_t t_off, t_width, t_desc;  // the order field's byte offset and width; 1: the largest ranks first
+  uint32_t t_pass, t_k;             // PREFIX / PICK: the pass (0: the most significant byte); min(k, 2^32 - 1)
+  uint32_t* bins;         // [kMtBins] zero between the passes
+  uint64_t* bitmap2;      // [tiles x kMsRounds] key == cut
+  uint32_t* tile2;        // [tiles] equals per tile (CUT), then the equals in front of the tile (SCAN)
 };
 inline uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
 
@@ -448,6 +477,88 @@ XE_HD void ms_expire_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t l
   if (sub == 0) o.recs[uint64_t(s) * o.rwords] = XE_SLOT_TOMB;  // a plain tombstone, its key words kept
 }
 
+
+// ---------------------------------------------------------------- top / evict / stats
+XE_HD void mo_add64(uint64_t* p, uint64_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_fetch_add((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *p += v;
+#endif
+}
+XE_HD void mo_max64(uint64_t* p, uint64_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_fetch_max((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  if (*p < v) *p = v;
+#endif
+}
+XE_HD uint64_t mt_mask(uint32_t width) { return width >= 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * width)) - 1; }
+// Is slot sbase + s eligible (ms_select_item's answer), and if so its rank key: the order field (0 under
+// VLEN0), complemented within the width when the largest ranks first.
+XE_HD bool mt_key_item(const XeMapOp& o, uint32_t s, uint64_t* key) {
+  const uint32_t at = o.sbase + s;
+  bool zero = false;
+  if (o.kind == XE_DM_HASH) {
+    const uint32_t st = uint32_t(o.recs[uint64_t(at) * o.rwords]);
+    if (!(st & XE_SLOT_FULL)) return false;
+    zero = (st & XE_SLOT_VLEN0) != 0;
+  }
+  const uint8_t* v = o.vals + uint64_t(at) * o.value_size;
+  if (o.f_op != kMfAll && !ms_filter(o.f_op, zero ? 0 : ms_field(v + o.f_off, o.f_width), o.f_operand)) return false;
+  const uint64_t f = zero ? 0 : ms_field(v + o.t_off, o.t_width);
+  *key = o.t_desc ? ~f & mt_mask(o.t_width) : f;
+  return true;
+}
+XE_HD uint64_t mt_prefix(const XeMapOp& o) { return uint64_t(o.ctr[kMtPrefix]) | uint64_t(o.ctr[kMtPrefix + 1]) << 32; }
+// PREFIX, pass t_pass: does the key share the bytes fixed so far, and the bin of its next byte.
+XE_HD bool mt_in_prefix(const XeMapOp& o, uint64_t key, uint64_t prefix) {
+  return o.t_pass == 0 || (key >> (8 * (o.t_width - o.t_pass))) == prefix;
+}
+XE_HD uint32_t mt_bin(const XeMapOp& o, uint64_t key) { return uint32_t(key >> (8 * (o.t_width - 1 - o.t_pass))) & 255u; }
+// PICK, bin b holding c keys with `before` keys in the bins in front of it: does the number needed run out here?
+XE_HD bool mt_pick_here(uint32_t need, uint32_t before, uint32_t c) { return need > before && need - before <= c; }
+XE_HD void mt_pick_write(const XeMapOp& o, uint32_t b, uint32_t need, uint32_t before) {
+  const uint64_t p = (o.t_pass ? mt_prefix(o) << 8 : 0) | b;
+  o.ctr[kMtPrefix] = uint32_t(p);
+  o.ctr[kMtPrefix + 1] = uint32_t(p >> 32);
+  o.ctr[kMtNeed] = need - before;
+}
+// CUT: 1: the key ranks in front of the cut; 2: it equals the cut; 0: neither, or nothing is needed.
+XE_HD uint32_t mt_cut_item(const XeMapOp& o, uint32_t s, uint64_t cut, uint32_t need) {
+  uint64_t key;
+  if (!need || !mt_key_item(o, s, &key)) return 0;
+  return key < cut ? 1u : key == cut ? 2u : 0u;
+}
+// TRIM: lane `lane` of a round whose equal bits are `word`, with `before` equals in front of the round.
+XE_HD bool mt_trim_item(uint32_t lane, uint64_t word, uint32_t before, uint32_t need) {
+  if (!((word >> lane) & 1)) return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t rank = before + __builtin_amdgcn_mbcnt_hi(uint32_t(word >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(word), 0));
+#else
+  const uint32_t rank = before + uint32_t(__builtin_popcountll(word & ((uint64_t(1) << lane) - 1)));
+#endif
+  return rank < need;
+}
+// STATS: one lane's running count, sum, ~min and max; and their way into the counters.
+struct XeMtStats { uint64_t count, sum, nmin, max; };
+XE_HD void mt_stats_item(const XeMapOp& o, uint32_t s, XeMtStats* a) {
+  uint64_t f;
+  if (!mt_key_item(o, s, &f)) return;  // (t_desc is 0: the key is the field)
+  a->count++;
+  a->sum += f;
+  a->nmin = a->nmin > ~f ? a->nmin : ~f;
+  a->max = a->max > f ? a->max : f;
+}
+XE_HD void mt_stats_flush(const XeMapOp& o, const XeMtStats& a) {
+  if (!a.count) return;
+  uint64_t* w = reinterpret_cast<uint64_t*>(o.ctr + kMtStats);
+  mo_add64(w, a.count);
+  mo_add64(w + 1, a.sum);
+  mo_max64(w + 2, a.nmin);
+  mo_max64(w + 3, a.max);
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
@@ -490,6 +601,77 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
         before += uint32_t(__builtin_popcountll(word));
       }
     }
+    return 0;
+  }
+  if (step == XE_MO_TOP_PREFIX) {
+    const uint64_t prefix = mt_prefix(o);
+    for (uint32_t s = 0; s < o.nslots; s++) {
+      uint64_t key;
+      if (mt_key_item(o, s, &key) && mt_in_prefix(o, key, prefix)) o.bins[mt_bin(o, key)]++;
+    }
+    return 0;
+  }
+  if (step == XE_MO_TOP_PICK) {
+    uint32_t need = o.ctr[kMtNeed];
+    if (o.t_pass == 0) {
+      uint32_t total = 0;
+      for (uint32_t b = 0; b < kMtBins; b++) total += o.bins[b];
+      o.ctr[kMtMatched] = total;
+      need = total < o.t_k ? total : o.t_k;
+    }
+    uint32_t before = 0;
+    for (uint32_t b = 0; b < kMtBins; b++) {
+      const uint32_t c = o.bins[b];
+      if (mt_pick_here(need, before, c)) mt_pick_write(o, b, need, before);
+      before += c;
+      o.bins[b] = 0;
+    }
+    return 0;
+  }
+  if (step == XE_MO_TOP_CUT) {
+    const uint64_t cut = mt_prefix(o);
+    const uint32_t need = o.ctr[kMtNeed];
+    for (uint32_t t = 0; t < tiles; t++) {
+      uint32_t c1 = 0, c2 = 0;
+      for (uint32_t r = 0; r < kMsRounds; r++) {
+        uint64_t w1 = 0, w2 = 0;
+        for (uint32_t lane = 0; lane < 64; lane++) {
+          const uint32_t s = t * kMsTile + r * 64 + lane;
+          const uint32_t c = s < o.nslots ? mt_cut_item(o, s, cut, need) : 0;
+          if (c == 1) w1 |= uint64_t(1) << lane;
+          if (c == 2) w2 |= uint64_t(1) << lane;
+        }
+        o.bitmap[uint64_t(t) * kMsRounds + r] = w1;
+        o.bitmap2[uint64_t(t) * kMsRounds + r] = w2;
+        c1 += uint32_t(__builtin_popcountll(w1));
+        c2 += uint32_t(__builtin_popcountll(w2));
+      }
+      o.tile[t] = c1;
+      o.tile2[t] = c2;
+    }
+    return 0;
+  }
+  if (step == XE_MO_TOP_TRIM) {
+    const uint32_t need = o.ctr[kMtNeed];
+    for (uint32_t t = 0; t < tiles; t++) {
+      uint32_t before = o.tile2[t], cnt = 0;
+      for (uint32_t r = 0; r < kMsRounds; r++) {
+        const uint64_t word = o.bitmap2[uint64_t(t) * kMsRounds + r];
+        uint64_t kept = 0;
+        for (uint32_t lane = 0; lane < 64; lane++)
+          if (mt_trim_item(lane, word, before, need)) kept |= uint64_t(1) << lane;
+        o.bitmap[uint64_t(t) * kMsRounds + r] |= kept;
+        cnt += uint32_t(__builtin_popcountll(kept));
+        before += uint32_t(__builtin_popcountll(word));
+      }
+      o.tile[t] += cnt;
+    }
+    return 0;
+  }
+  if (step == XE_MO_TOP_STATS) {
+    XeMtStats a{};
+    for (uint32_t s = 0; s < o.nslots; s++) mt_stats_item(o, s, &a);
+    mt_stats_flush(o, a);
     return 0;
   }
   for (uint32_t i = 0; i < o.n; i++) {

@@ -1,6 +1,6 @@
-// Device-resident batched map lookup, update and delete (xe_mapops.h: the steps and what each one
-// decides). One kernel per step; a step works either one batch entry per lane (probes, claims, marks) or
-// one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
+// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats (xe_mapops.h:
+// the steps and what each one decides). One kernel per step; a step works either one batch entry per lane
+// (probes, claims, marks) or one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
 // destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
 // one-workgroup prefix sum of the tile counts (SCAN); their COPY and EXPIRE are value kernels.
 //
@@ -196,9 +196,162 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapscan_scatter_kernel(XeMapOp 
   }
 }
 
+// ---- top / evict / stats. PREFIX, CUT, TRIM and STATS keep SELECT's shape (a wave per tile, four
+// independent rounds, the waves striding over the tiles).
+//
+// PREFIX: the workgroup's 256 bins live in LDS. A flow table's counters leave most of a wide field's high
+// bytes zero, so a round's keys usually share one bin: the first eligible lane's bin is counted once for
+// the wave (one LDS atomic instead of 64 to one address), the lanes in other bins add on their own.
+__global__ void __launch_bounds__(kMoThreads) xe_maptop_prefix_kernel(XeMapOp o, uint32_t tiles) {
+  __shared__ uint32_t hist[kMtBins];
+  static_assert(kMtBins == kMoThreads, "one bin per thread");
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t prefix = mt_prefix(o);
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint64_t key[kMsRounds];
+    bool in[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      key[r] = 0;
+      in[r] = s < o.nslots && mt_key_item(o, s, &key[r]) && mt_in_prefix(o, key[r], prefix);
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const unsigned long long act = __ballot(in[r]);
+      if (!act) continue;
+      const uint32_t bin = mt_bin(o, key[r]);
+      const uint32_t lead = uint32_t(__builtin_ctzll(act)), lbin = uint32_t(__shfl(int(bin), int(lead), 64));
+      const unsigned long long same = __ballot(in[r] && bin == lbin);
+      if (lane == lead) atomicAdd(&hist[lbin], uint32_t(__popcll(same)));
+      else if (in[r] && bin != lbin) atomicAdd(&hist[bin], 1u);
+    }
+  }
+  __syncthreads();
+  const uint32_t c = hist[threadIdx.x];
+  if (c) mo_add32(o.bins + threadIdx.x, c);
+}
+
+// PICK: one bin per thread; the exclusive sums of the bins as in xe_mapscan_scan_kernel.
+__global__ void __launch_bounds__(kMtBins) xe_maptop_pick_kernel(XeMapOp o) {
+  constexpr uint32_t kWaves = kMtBins / 64;
+  __shared__ uint32_t wsum[kWaves];
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint32_t c = o.bins[t];
+  uint32_t need = o.ctr[kMtNeed];
+  uint32_t inc = c;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += y;
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();  // (also: every thread has read the counters before one of them writes)
+  uint32_t before = inc - c, total = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kWaves; k++) {
+    const uint32_t s = wsum[k];
+    before += k < w ? s : 0;
+    total += s;
+  }
+  if (o.t_pass == 0) {
+    need = total < o.t_k ? total : o.t_k;
+    if (t == 0) o.ctr[kMtMatched] = total;
+  }
+  if (mt_pick_here(need, before, c)) mt_pick_write(o, t, need, before);
+  o.bins[t] = 0;
+}
+
+__global__ void __launch_bounds__(kMoThreads) xe_maptop_cut_kernel(XeMapOp o, uint32_t tiles) {
+  const uint64_t cut = mt_prefix(o);
+  const uint32_t need = o.ctr[kMtNeed];
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint32_t c[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      c[r] = s < o.nslots ? mt_cut_item(o, s, cut, need) : 0;
+    }
+    uint32_t c1 = 0, c2 = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const unsigned long long b1 = __ballot(c[r] == 1), b2 = __ballot(c[r] == 2);
+      if (lane == 0) {
+        o.bitmap[uint64_t(t) * kMsRounds + r] = b1;
+        o.bitmap2[uint64_t(t) * kMsRounds + r] = b2;
+      }
+      c1 += uint32_t(__popcll(b1));
+      c2 += uint32_t(__popcll(b2));
+    }
+    if (lane == 0) {
+      o.tile[t] = c1;
+      o.tile2[t] = c2;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kMoThreads) xe_maptop_trim_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t need = o.ctr[kMtNeed];
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint32_t before = o.tile2[t];
+    if (before >= need) continue;  // every equal to keep lies in front of this tile
+    uint64_t word[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap2[uint64_t(t) * kMsRounds + r];
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const unsigned long long kept = __ballot(mt_trim_item(lane, word[r], before, need));
+      if (lane == 0 && kept) o.bitmap[uint64_t(t) * kMsRounds + r] |= kept;
+      cnt += uint32_t(__popcll(kept));
+      before += uint32_t(__popcll(word[r]));
+    }
+    if (lane == 0 && cnt) o.tile[t] += cnt;
+  }
+}
+
+__global__ void __launch_bounds__(kMoThreads) xe_maptop_stats_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  XeMtStats a{};
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      if (s < o.nslots) mt_stats_item(o, s, &a);
+    }
+  }
+#pragma unroll
+  for (uint32_t d = 32; d; d >>= 1) {
+    const uint64_t cn = __shfl_xor((unsigned long long)a.count, int(d), 64), sm = __shfl_xor((unsigned long long)a.sum, int(d), 64);
+    const uint64_t mn = __shfl_xor((unsigned long long)a.nmin, int(d), 64), mx = __shfl_xor((unsigned long long)a.max, int(d), 64);
+    a.count += cn;
+    a.sum += sm;
+    a.nmin = a.nmin > mn ? a.nmin : mn;
+    a.max = a.max > mx ? a.max : mx;
+  }
+  // the waves of a workgroup meet in LDS: the atomics all go to the same four words, so fewer is faster
+  __shared__ XeMtStats part[kMoThreads / 64];
+  if (lane == 0) part[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (uint32_t w = 1; w < kMoThreads / 64; w++) {
+      a.count += part[w].count;
+      a.sum += part[w].sum;
+      a.nmin = a.nmin > part[w].nmin ? a.nmin : part[w].nmin;
+      a.max = a.max > part[w].max ? a.max : part[w].max;
+    }
+    mt_stats_flush(o, a);
+  }
+}
+
 }  // namespace
 
-// SELECT / SCATTER: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
+// SELECT / SCATTER and the tile passes of top / evict / stats: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
 // would take, between kMoOneTurn and kMoMaxBlocks (the file's policy), the waves striding over the tiles.
 static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
   const uint32_t tiles = xe_ms_tiles(op->nslots);
@@ -207,16 +360,25 @@ static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
     hipLaunchKernelGGL(xe_mapscan_scan_kernel, dim3(1), dim3(kMsScanThreads), 0, s, *op, tiles);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
+  if (step == XE_MO_TOP_PICK) {
+    hipLaunchKernelGGL(xe_maptop_pick_kernel, dim3(1), dim3(kMtBins), 0, s, *op);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
   const uint32_t want = (tiles + kMoThreads / 64 - 1) / (kMoThreads / 64);
   const uint32_t blocks = want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks;
   if (step == XE_MO_SCAN_SELECT) hipLaunchKernelGGL(xe_mapscan_select_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_TOP_PREFIX) hipLaunchKernelGGL(xe_maptop_prefix_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_TOP_CUT) hipLaunchKernelGGL(xe_maptop_cut_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_TOP_TRIM) hipLaunchKernelGGL(xe_maptop_trim_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_TOP_STATS) hipLaunchKernelGGL(xe_maptop_stats_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   else hipLaunchKernelGGL(xe_mapscan_scatter_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream) {
   hipStream_t s = hipStream_t(stream);
-  if (step == XE_MO_SCAN_SELECT || step == XE_MO_SCAN_SCAN || step == XE_MO_SCAN_SCATTER) return launch_mapscan(op, step, s);
+  if (step == XE_MO_SCAN_SELECT || step == XE_MO_SCAN_SCAN || step == XE_MO_SCAN_SCATTER || step >= XE_MO_TOP_PREFIX)
+    return launch_mapscan(op, step, s);
   if (!op->n) return 0;
   const bool value = step == XE_MO_LOOKUP_VALUE || step == XE_MO_UPDATE_COPY || step == XE_MO_DELETE_ZERO ||
                      step == XE_MO_SCAN_COPY || step == XE_MO_SCAN_EXPIRE;

@@ -4474,15 +4474,9 @@ int xe_map_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count,
 // Scan and expire (xe_mapops.h SELECT .. EXPIRE). host: keys / values are host memory, staged through
 // d_mo_keys / d_mo_vals once r is known. The per-entry scratch and the staging hold r entries, never
 // cap_entries or the table.
-static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
-                        uint64_t* matched, void* stream, bool expire, bool host) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  const int rc = mapop_begin(vm, mi, 1, expire, host ? nullptr : stream, &m, &o, &s);  // (the counters; slots come with r)
-  if (rc < 0) return rc;
-  if (expire && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
-  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+//
+// The filter checked and set, and the slots a tile pass looks at.
+static int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp& o) {
   const xe_map_filter all{};  // XE_MF_ALL
   if (!f) f = &all;
   if (f->op >= kMfOps) return fail(vm, XE_ERR_INVAL, "map filter: unknown op");
@@ -4498,19 +4492,14 @@ static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* key
   if (m->dkind == XE_DM_ARRAY) o.nslots = m->def.max_entries;
   else if (m->def.key_size == 0) o.sbase = m->cap, o.nslots = 1;  // the empty key: the one record past the table
   else o.nslots = m->cap;
-  *matched = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (!tiles) return XE_OK;
-  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
-  o.bitmap = (uint64_t*)vm->d_ms;
-  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds);
-  if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
-  uint32_t total = 0;
-  if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map scan");
-  *matched = total;
-  const uint32_t r = uint32_t(std::min<uint64_t>(total, cap_entries));
+  return XE_OK;
+}
+// The r entries the bitmap and the tile bases select: SCATTER, COPY, (remove) EXPIRE, the staging back to
+// the host, the synchronisation and the host's view of a map that lost entries.
+static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uint32_t r, void* keys, void* values, bool remove,
+                           bool host, const char* what) {
   const bool out = keys || values;
-  if (!r || (!expire && !out)) return XE_OK;
+  if (!r || (!remove && !out)) return XE_OK;
   const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size;
   if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
   o.ctr = (uint32_t*)vm->d_mo;
@@ -4524,18 +4513,117 @@ static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* key
   if (out)
     if (int e = mapop_steps(vm, o, {XE_MO_SCAN_COPY}, s)) return e;
   uint32_t cnt = 0;
-  if (expire) {
+  if (remove) {
     if (int e = mapop_steps(vm, o, {XE_MO_SCAN_EXPIRE}, s)) return e;
-    if (d2h(&cnt, m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, "map expire");
+    if (d2h(&cnt, m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, what);
   }
   if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s))))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
-  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, expire ? "map expire" : "map scan");
-  if (expire) {
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+  if (remove) {
     m->live = cnt;
     m->dev_dirty = true;
     vm->staged_slot = -1;
   }
+  return XE_OK;
+}
+static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
+                        uint64_t* matched, void* stream, bool expire, bool host) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const int rc = mapop_begin(vm, mi, 1, expire, host ? nullptr : stream, &m, &o, &s);  // (the counters; slots come with r)
+  if (rc < 0) return rc;
+  if (expire && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  *matched = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return XE_OK;
+  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
+  o.bitmap = (uint64_t*)vm->d_ms;
+  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds);
+  if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
+  uint32_t total = 0;
+  if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map scan");
+  *matched = total;
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), keys, values, expire, host,
+                         expire ? "map expire" : "map scan");
+}
+
+// Top and evict (xe_mapops.h PREFIX .. TRIM, then the scan's steps): everything up to the final SCAN is
+// queued without a readback; the counters then give matched, the cut and r in one copy.
+static int map_order_check(xe_vm* vm, HostMap* m, const xe_map_order* ord, XeMapOp& o) {
+  if (!ord) return fail(vm, XE_ERR_INVAL, "null map order");
+  if (ord->width != 1 && ord->width != 2 && ord->width != 4 && ord->width != 8) return fail(vm, XE_ERR_INVAL, "map order: width must be 1, 2, 4 or 8");
+  if (ord->pad) return fail(vm, XE_ERR_INVAL, "map order: pad must be 0");
+  if (ord->descending > 1) return fail(vm, XE_ERR_INVAL, "map order: descending must be 0 or 1");
+  if (uint64_t(ord->offset) + ord->width > m->def.value_size) return fail(vm, XE_ERR_INVAL, "map order: the field lies outside the value");
+  o.t_off = ord->offset;
+  o.t_width = ord->width;
+  o.t_desc = ord->descending;
+  return XE_OK;
+}
+static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
+                       uint64_t* matched, uint64_t* cut, void* stream, bool evict, bool host) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const int rc = mapop_begin(vm, mi, 1, evict, host ? nullptr : stream, &m, &o, &s);
+  if (rc < 0) return rc;
+  if (evict && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  if (int e = map_order_check(vm, m, ord, o)) return e;
+  *matched = 0;
+  if (cut) *cut = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return XE_OK;
+  // two bitmaps, two tile-count arrays, the bins
+  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * 2 * (kMsRounds * 8 + 4) + kMtBins * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
+  o.bitmap = (uint64_t*)vm->d_ms;
+  o.bitmap2 = o.bitmap + tiles * kMsRounds;
+  o.tile = (uint32_t*)(o.bitmap2 + tiles * kMsRounds);
+  o.tile2 = o.tile + tiles;
+  o.bins = o.tile2 + tiles;
+  o.t_k = uint32_t(std::min<uint64_t>(k, 0xffffffffu));  // (more than any table holds)
+  if (dmemset(o.bins, 0, kMtBins * 4, s)) return fail(vm, XE_ERR_DEVICE, "map top");
+  for (o.t_pass = 0; o.t_pass < o.t_width; o.t_pass++)
+    if (int e = mapop_steps(vm, o, {XE_MO_TOP_PREFIX, XE_MO_TOP_PICK}, s)) return e;
+  XeMapOp eq = o;  // the scan's SCAN over the equal counts
+  eq.tile = o.tile2;
+  if (int e = mapop_steps(vm, o, {XE_MO_TOP_CUT}, s)) return e;
+  if (int e = mapop_steps(vm, eq, {XE_MO_SCAN_SCAN}, s)) return e;
+  if (int e = mapop_steps(vm, o, {XE_MO_TOP_TRIM, XE_MO_SCAN_SCAN}, s)) return e;
+  uint32_t ctr[kMoCounters];
+  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map top");
+  *matched = ctr[kMtMatched];
+  const uint32_t r = ctr[kMoMatched];
+  if (cut && r) {
+    const uint64_t key = uint64_t(ctr[kMtPrefix]) | uint64_t(ctr[kMtPrefix + 1]) << 32;
+    *cut = o.t_desc ? ~key & mt_mask(o.t_width) : key;
+  }
+  return map_scan_report(vm, m, o, s, r, keys, values, evict, host, evict ? "map evict" : "map top");
+}
+static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const int rc = mapop_begin(vm, mi, 1, false, stream, &m, &o, &s);
+  if (rc < 0) return rc;
+  if (!out) return fail(vm, XE_ERR_INVAL, "null stats");
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  if (int e = map_order_check(vm, m, field, o)) return e;
+  o.t_desc = 0;
+  uint64_t w[4] = {0, 0, 0, 0};  // count, sum, ~min, max
+  if (xe_ms_tiles(o.nslots)) {
+    if (int e = mapop_steps(vm, o, {XE_MO_TOP_STATS}, s)) return e;
+    if (d2h(w, o.ctr + kMtStats, sizeof w, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map stats");
+  }
+  out->count = w[0];
+  out->sum = w[1];
+  out->min = ~w[2];
+  out->max = w[3];
   return XE_OK;
 }
 
@@ -4552,6 +4640,26 @@ int xe_map_scan(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void*
 }
 int xe_map_expire(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries, uint64_t* matched) {
   return map_scan_run(vm, mi, f, keys, values, cap_entries, matched, nullptr, true, true);
+}
+
+int xe_map_top_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* d_keys, void* d_values, uint64_t k,
+                      uint64_t* matched, uint64_t* cut, void* stream) {
+  return map_top_run(vm, mi, f, ord, d_keys, d_values, k, matched, cut, stream, false, false);
+}
+int xe_map_evict_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* d_keys, void* d_values, uint64_t k,
+                        uint64_t* matched, uint64_t* cut, void* stream) {
+  return map_top_run(vm, mi, f, ord, d_keys, d_values, k, matched, cut, stream, true, false);
+}
+int xe_map_top(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
+               uint64_t* matched, uint64_t* cut) {
+  return map_top_run(vm, mi, f, ord, keys, values, k, matched, cut, nullptr, false, true);
+}
+int xe_map_evict(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
+                 uint64_t* matched, uint64_t* cut) {
+  return map_top_run(vm, mi, f, ord, keys, values, k, matched, cut, nullptr, true, true);
+}
+int xe_map_stats(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
+  return map_stats_run(vm, mi, f, field, out, stream);
 }
 
 int xe_debug_map_traffic(xe_vm* vm, int32_t mi, uint64_t* uploads, uint64_t* downloads) {

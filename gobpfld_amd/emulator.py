@@ -62,6 +62,15 @@ class MapFilter:
 
 
 @dataclass
+class MapOrder:
+    """xe_map_order: rank by the unsigned little-endian field of `width` bytes at byte `offset` of the
+    value, largest first when `descending` (VM.map_top / VM.map_evict; the field of VM.map_stats)."""
+    offset: int = 0
+    width: int = 8
+    descending: bool = True
+
+
+@dataclass
 class Settings:
     max_steps: int = 1 << 20
     ingress_ifindex: int = 1
@@ -376,6 +385,70 @@ class VM:
     def map_expire(self, m: int, flt: "MapFilter | None" = None, cap: int | None = None, on_device: bool = False):
         """map_scan that also removes the r entries it returns (HASH; xe_map_expire_device)."""
         return self._map_scan(m, flt, cap, on_device, True)
+
+    # ---- top-K, evict and statistics on the device copy (xe_map_top_device / xe_map_evict_device / xe_map_stats)
+    def _map_top(self, m: int, order: "MapOrder", k: int, flt, on_device: bool, ranked: bool, evict: bool):
+        d = self.map_defs[m]
+        ks = 4 if d.type in ARRAY_TYPES else d.key_size
+        what = "map evict" if evict else "map top"
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        fp = None if cf is None else C.byref(cf)
+        co = N.MapOrder(order.offset, order.width, int(order.descending), 0)
+        n, cut = C.c_uint64(0), C.c_uint64(0)
+        room = min(k, d.max_entries)  # (r <= matched <= max_entries: no buffer of k entries for a huge k)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.settings.device)
+            torch.cuda.current_stream(dev).synchronize()  # the calls run on the VM's stream
+            keys = torch.empty((room, ks), dtype=torch.uint8, device=dev)
+            vals = torch.empty((room, d.value_size), dtype=torch.uint8, device=dev)
+            fn = self.lib.map_evict_device if evict else self.lib.map_top_device
+            rc = fn(self.h, m, fp, C.byref(co), keys.data_ptr() or None, vals.data_ptr() or None, k, C.byref(n), C.byref(cut), None)
+        else:
+            keys = np.zeros((room, ks), dtype=np.uint8)
+            vals = np.zeros((room, d.value_size), dtype=np.uint8)
+            fn = self.lib.map_evict if evict else self.lib.map_top
+            rc = fn(self.h, m, fp, C.byref(co), keys.ctypes.data if room else None, vals.ctypes.data if room else None, k,
+                    C.byref(n), C.byref(cut))
+        self._check(rc, what)
+        r = min(int(n.value), k)
+        keys, vals = keys[:r], vals[:r]
+        if ranked and r > 1:  # the call reports in slot order: a stable sort on the field keeps the tie order
+            if on_device:
+                f = torch.zeros(r, dtype=torch.int64, device=dev)
+                for b in range(order.width):
+                    f |= vals[:, order.offset + b].to(torch.int64) << (8 * b)
+                f ^= torch.tensor(-(1 << 63), dtype=torch.int64, device=dev)  # unsigned order through signed compares
+                if order.descending:
+                    f = ~f
+                idx = torch.sort(f, stable=True).indices
+            else:
+                f = np.zeros(r, dtype=np.uint64)
+                for b in range(order.width):
+                    f |= vals[:, order.offset + b].astype(np.uint64) << np.uint64(8 * b)
+                idx = np.argsort(~f if order.descending else f, kind="stable")
+            keys, vals = keys[idx], vals[idx]
+        return keys, vals, int(n.value), int(cut.value)
+
+    def map_top(self, m: int, order: "MapOrder", k: int, flt: "MapFilter | None" = None, on_device: bool = False,
+                ranked: bool = True):
+        """(keys[r], values[r], matched, cut): the r = min(k, matched) entries that rank first by `order`
+        among those `flt` selects (equal fields in slot order); cut is the r-th entry's field. ranked: rows
+        in rank order; otherwise in the slot order the call reports. on_device: CUDA tensors."""
+        return self._map_top(m, order, k, flt, on_device, ranked, False)
+
+    def map_evict(self, m: int, order: "MapOrder", k: int, flt: "MapFilter | None" = None, on_device: bool = False,
+                  ranked: bool = True):
+        """map_top that also removes the r entries it returns (HASH; xe_map_evict_device)."""
+        return self._map_top(m, order, k, flt, on_device, ranked, True)
+
+    def map_stats(self, m: int, field: "MapOrder", flt: "MapFilter | None" = None) -> dict:
+        """{count, sum (mod 2^64), min, max} of `field` over the entries `flt` selects (xe_map_stats)."""
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        co = N.MapOrder(field.offset, field.width, 0, 0)
+        out = N.MapStats()
+        self._check(self.lib.map_stats(self.h, m, None if cf is None else C.byref(cf), C.byref(co), C.byref(out), None), "map stats")
+        return {"count": out.count, "sum": out.sum, "min": out.min, "max": out.max}
 
     def map_traffic(self, m: int) -> tuple[int, int]:
         """xe_debug_map_traffic: (uploads, downloads) of the whole map so far."""

@@ -440,6 +440,53 @@ int xe_map_scan(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* keys, 
 int xe_map_expire(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
                   uint64_t* matched);
 
+/* --- top-K, evict and value statistics on the device copy (ARRAY and HASH kinds): the k entries that rank
+ * first by one field of the value, their removal, and the count, sum, minimum and maximum of a field, by
+ * kernels that read the slot table at device bandwidth; only the selected entries leave the device. The
+ * rules of the scan block above hold unchanged (xe_sync first, one upload of a host-dirty map, finished on
+ * return, stream NULL is the VM's stream, d_* are device addresses, the same four map types are
+ * XE_ERR_UNSUPPORTED, the filter and its errors are the scan's).
+ *
+ *   eligible: the entries xe_map_scan_device would report for `f`; *matched = their number (NULL:
+ *             XE_ERR_INVAL).
+ *   rank:     by the order field (`width` bytes at byte `offset` of the value, any alignment, little endian,
+ *             zero-extended, compared unsigned; a nil-backed value ranks as field 0), largest first when
+ *             `descending` is 1, smallest first when 0; equal fields rank in ascending slot order (ARRAY:
+ *             index order). The rank is total: the answer is a function of the map's state alone.
+ *   selected: the first r = min(k, *matched) entries of the rank. *cut (may be NULL) = the order field of
+ *             the r-th ranked entry, 0 when r == 0.
+ *   output:   the selected entries go to d_keys (r x key_size; ARRAY: r x 4) and d_values (r x value_size)
+ *             in ascending slot order, the order a scan reports them in, NOT in rank order: a caller that
+ *             wants them ranked sorts the r rows by the field (a stable sort keeps the tie order). No byte
+ *             past entry r is written; either pointer may be NULL; k == 0 only counts.
+ *   evict:    HASH kinds only (ARRAY: XE_ERR_INVAL). Removes exactly the r entries it reports and reports
+ *             their values from before the removal; each record is left as xe_map_expire_device leaves one.
+ *             Refused with XE_ERR_INVAL while a shard epoch is open; top and stats change no state and are
+ *             allowed there.
+ *   stats:    over the eligible entries' `field` (its `descending` is ignored): count (== matched), sum
+ *             modulo 2^64, min (UINT64_MAX when count == 0), max (0 when count == 0). `out` is host memory.
+ *   errors:   ord NULL, a width other than 1, 2, 4 or 8, pad != 0, descending > 1, or a field that does
+ *             not lie inside value_size: XE_ERR_INVAL. */
+typedef struct xe_map_order {
+  uint32_t offset;      /* byte offset of the order field inside the value; any alignment */
+  uint32_t width;       /* 1, 2, 4 or 8 bytes, little endian, unsigned */
+  uint32_t descending;  /* 1: largest first; 0: smallest first */
+  uint32_t pad;         /* 0 */
+} xe_map_order;
+/* (no typedef: C keeps the function of the same name among the ordinary identifiers) */
+struct xe_map_stats { uint64_t count, sum, min, max; };
+int xe_map_top_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_order* ord, void* d_keys,
+                      void* d_values, uint64_t k, uint64_t* matched, uint64_t* cut, void* stream);
+int xe_map_evict_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_order* ord, void* d_keys,
+                        void* d_values, uint64_t k, uint64_t* matched, uint64_t* cut, void* stream);
+/* The same with host pointers: the r selected entries are staged through device buffers of the VM. */
+int xe_map_top(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values,
+               uint64_t k, uint64_t* matched, uint64_t* cut);
+int xe_map_evict(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values,
+                 uint64_t k, uint64_t* matched, uint64_t* cut);
+int xe_map_stats(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_order* field,
+                 struct xe_map_stats* out, void* stream);
+
 /* --- one process, N devices (SURVEY §8b xe_run_batch_multi): the Go host shards a batch over the
  * GPUs of a node through the FFI alone. vms[k] runs on its own device with identical programs, maps
  * and map contents (the caller sets each up the same way). Exchange over RCCL (xGMI) when the devices
