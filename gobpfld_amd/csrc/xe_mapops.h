@@ -1,6 +1,6 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
 // xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device,
-// xe_map_top_device, xe_map_evict_device, xe_map_stats): the per-key and per-slot decision logic that the kernels
+// xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group): the per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
 // declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
 //
@@ -59,6 +59,24 @@
 //   stats    STATS   one tile pass: count, sum, min and max of the field per lane, reduced across the wave and
 //                    the workgroup, one 64-bit atomic each per workgroup (integers: the order of arrival
 //                    does not matter)
+//   group    SELECT, SCAN   (the scan's, on the source: the bitmap, matched)
+//            LOCATE  a tile pass over the source bitmap: a selected slot assembles its group key (some bytes of
+//                    its key or value, zero-padded as mo_load_key pads a key) and finds or claims the
+//                    destination record with update LOCATE's protocol; the claim names the claiming SOURCE
+//                    slot (BUSY | (slot + 1) << 32), so a lane that meets a claim compares its group key with
+//                    that slot's — the source is only read during the call — and never waits. A FULL
+//                    nil-backed (VLEN0) record of the group is claimed too, so that it can be zeroed. Claims
+//                    of free and tombstone records are counted (kMoNew). No per-entry scratch: the later
+//                    passes probe again
+//            UNDO    (the groups do not fit, or an ARRAY index is out of range) a tile pass over the
+//                    destination table: every BUSY record is what it was
+//            PUBLISH a tile pass over the destination table: a BUSY record gets its key words (rebuilt from
+//                    the source slot it names; a tombstone holds them), a zero value in the map and the delta
+//                    base, and becomes plain FULL; the count rises by the counted claims
+//            ADD     a tile pass over the source bitmap again: a read-only probe (every record is FULL now),
+//                    then 64-bit atomic adds of the count and the measure into the map and the delta base.
+//                    The kernel combines the lanes of a wave that share a destination slot first, for up to
+//                    kMgLeaders distinct slots a round
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
 // an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
@@ -83,6 +101,7 @@ enum : uint32_t {
   XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO,
   XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN, XE_MO_SCAN_SCATTER, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE,
   XE_MO_TOP_PREFIX, XE_MO_TOP_PICK, XE_MO_TOP_CUT, XE_MO_TOP_TRIM, XE_MO_TOP_STATS,
+  XE_MO_GROUP_LOCATE, XE_MO_GROUP_UNDO, XE_MO_GROUP_PUBLISH, XE_MO_GROUP_ADD,
   XE_MO_STEPS
 };
 
@@ -100,6 +119,13 @@ constexpr uint32_t kMoErrRange = 1, kMoErrFull = 2;  // an ARRAY index out of ra
 // scan / expire: a tile is kMsTile consecutive slots, one wave's work in kMsRounds rounds of 64; the SCAN
 // step sums kMsScanPass tile counts a pass (262,144 slots: a table of 2^20 slots takes four passes)
 constexpr uint32_t kMsRounds = 4, kMsTile = 64 * kMsRounds, kMsScanThreads = 256, kMsScanPass = kMsScanThreads * 4;
+// group: GROUP_ADD combines the lanes of a wave that share a destination slot for this many distinct slots a
+// round (the first remaining lane leads each time), the lanes left over add singly. 0: every lane adds singly
+// (a -D of the tuning build, for the profile's comparison)
+#ifndef XE_MG_LEADERS
+#define XE_MG_LEADERS 4
+#endif
+constexpr uint32_t kMgLeaders = XE_MG_LEADERS, kMgNone = 0xffffffffu;
 // the filter's ops (include/xdpemu.h XE_MF_*)
 enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
 
@@ -131,6 +157,15 @@ struct XeMapOp {
   uint32_t* bins;         // [kMtBins] zero between the passes
   uint64_t* bitmap2;      // [tiles x kMsRounds] key == cut
   uint32_t* tile2;        // [tiles] equals per tile (CUT), then the equals in front of the tile (SCAN)
+  // group: the destination map beside the source above (mg_dst makes an XeMapOp of it for the probes)
+  uint32_t g_kind, g_key_size, g_value_size, g_max_entries, g_cap, g_kwords, g_rwords;
+  uint32_t g_from, g_off, g_len;     // the group bytes: 0 the source key / 1 the source value, first byte, number
+  uint32_t g_moff, g_mwidth;         // the measure in the source value (width 0: none)
+  uint32_t g_count_off, g_sum_off;   // the accumulators in the destination value (kMgNone: none)
+  uint64_t* g_recs;
+  uint8_t* g_vals;
+  uint8_t* g_snap;
+  uint32_t* g_count;
 };
 inline uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
 
@@ -559,6 +594,154 @@ XE_HD void mt_stats_flush(const XeMapOp& o, const XeMtStats& a) {
   mo_max64(w + 3, a.max);
 }
 
+// ---------------------------------------------------------------- group
+// The destination as an XeMapOp of its own: what mo_find and mo_key_eq read.
+XE_HD XeMapOp mg_dst(const XeMapOp& o) {
+  XeMapOp d{};
+  d.kind = o.g_kind;
+  d.key_size = o.g_key_size;
+  d.value_size = o.g_value_size;
+  d.max_entries = o.g_max_entries;
+  d.cap = o.g_cap;
+  d.kwords = o.g_kwords;
+  d.rwords = o.g_rwords;
+  d.recs = o.g_recs;
+  d.vals = o.g_vals;
+  d.snap = o.g_snap;
+  d.count = o.g_count;
+  d.ctr = o.ctr;
+  return d;
+}
+// Is the value of source slot `at` nil-backed (it then reads as zeros)?
+XE_HD bool mg_src_zero(const XeMapOp& o, uint32_t at) {
+  return o.kind == XE_DM_HASH && (uint32_t(o.recs[uint64_t(at) * o.rwords]) & XE_SLOT_VLEN0) != 0;
+}
+// The group key of source slot `at` (sbase included) as zero-padded words, as mo_load_key makes a key's: g_len
+// bytes at g_off of the slot's key (ARRAY: its index as a u32) or of its value. An ARRAY destination's index
+// is word 0 (g_len <= 4: zero-extended).
+XE_HD void mg_group_key(const XeMapOp& o, uint32_t at, uint64_t* kw) {
+  for (uint32_t w = 0; w < XE_MAX_KEY / 8; w++) kw[w] = 0;
+  if (o.g_from == 0 && o.kind == XE_DM_ARRAY) {  // (g_off + g_len <= 4)
+    kw[0] = (uint64_t(at) >> (8 * o.g_off)) & mt_mask(o.g_len);
+    return;
+  }
+  if (o.g_from != 0 && mg_src_zero(o, at)) return;
+  const uint8_t* p = (o.g_from == 0 ? reinterpret_cast<const uint8_t*>(o.recs + uint64_t(at) * o.rwords + 1)
+                                    : o.vals + uint64_t(at) * o.value_size) + o.g_off;
+  if (!(o.g_len & 7) && !(uintptr_t(p) & 7)) {
+    for (uint32_t w = 0; w < XE_MAX_KEY / 8; w++)
+      if (w * 8 < o.g_len) kw[w] = reinterpret_cast<const uint64_t*>(p)[w];
+    return;
+  }
+  for (uint32_t w = 0; w < XE_MAX_KEY / 8; w++) {
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < 8; b++)
+      if (w * 8 + b < o.g_len) v |= uint64_t(p[w * 8 + b]) << (8 * b);
+    kw[w] = v;
+  }
+}
+XE_HD uint64_t mg_measure(const XeMapOp& o, uint32_t at) {
+  if (!o.g_mwidth || mg_src_zero(o, at)) return 0;
+  return ms_field(o.vals + uint64_t(at) * o.value_size + o.g_moff, o.g_mwidth);
+}
+// LOCATE: the destination record of source slot sbase + s's group, or one claimed for it: mo_update_locate_item's
+// walk over the destination with the claim naming the source slot. True: this slot claimed a free or a
+// tombstone record (the caller counts them). An ARRAY destination only has its index checked.
+XE_HD bool mg_locate_item(const XeMapOp& o, uint32_t s) {
+  const uint32_t at = o.sbase + s;
+  uint64_t kw[XE_MAX_KEY / 8];
+  mg_group_key(o, at, kw);
+  if (o.g_kind == XE_DM_ARRAY) {
+    if (kw[0] >= o.g_max_entries) mo_or32(o.ctr + kMoErr, kMoErrRange);
+    return false;
+  }
+  const XeMapOp d = mg_dst(o);
+  const uint64_t own = XE_SLOT_BUSY | ((uint64_t(at) + 1) << 32);
+  const uint32_t mask = d.cap - 1;
+  uint32_t idx = uint32_t(xe_hash_words(kw, d.kwords, d.key_size)) & mask;
+  for (uint32_t probe = 0; probe < d.cap;) {
+    uint64_t* r = d.recs + uint64_t(idx) * d.rwords;
+    const uint64_t w0 = mo_load64(r);
+    const uint32_t st = uint32_t(w0);
+    if (st & XE_SLOT_FULL) {
+      if (mo_key_eq(d, r, kw)) {
+        if (!(st & XE_SLOT_VLEN0) || (st & XE_SLOT_BUSY)) return false;
+        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) return false;  // nil-backed: claimed to be zeroed, not counted
+        continue;  // lost it (to another slot of this group): look again
+      }
+    } else if (st & XE_SLOT_TOMB) {  // holds key words
+      if (mo_key_eq(d, r, kw)) {
+        if (st & XE_SLOT_BUSY) return false;
+        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) return true;
+        continue;
+      }
+    } else if (st & XE_SLOT_BUSY) {  // claimed in this launch by the source slot it names
+      uint64_t kj[XE_MAX_KEY / 8];
+      const uint32_t j = uint32_t(w0 >> 32) - 1;
+      bool eq = j >= o.sbase && j - o.sbase < o.nslots;
+      if (eq) {
+        mg_group_key(o, j, kj);
+        for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++) eq = eq && kj[k] == kw[k];
+      }
+      if (eq) return false;
+    } else {  // free
+      if (mo_cas64(r, w0, own) == w0) return true;
+      continue;
+    }
+    idx = (idx + 1) & mask;
+    probe++;
+  }
+  mo_or32(o.ctr + kMoErr, kMoErrFull);
+  return false;
+}
+// UNDO, destination slot ds: a claimed record is what it was (the high half of word 0 was zero).
+XE_HD void mg_undo_item(const XeMapOp& o, uint32_t ds) {
+  uint64_t* r = o.g_recs + uint64_t(ds) * o.g_rwords;
+  const uint32_t st = uint32_t(r[0]);
+  if (st & XE_SLOT_BUSY) r[0] = uint64_t(st & ~XE_SLOT_BUSY);
+}
+// PUBLISH, destination slot ds, lane `sub` of the `lanes` that share it: nothing unless the record is claimed.
+XE_HD bool mg_claimed(const XeMapOp& o, uint32_t ds) { return (uint32_t(o.g_recs[uint64_t(ds) * o.g_rwords]) & XE_SLOT_BUSY) != 0; }
+XE_HD void mg_publish_item(const XeMapOp& o, uint32_t ds, uint32_t sub, uint32_t lanes) {
+  uint64_t* r = o.g_recs + uint64_t(ds) * o.g_rwords;
+  const uint64_t w0 = r[0];
+  const uint32_t st = uint32_t(w0);
+  // the value: zero in the map and in the delta base (a tombstone's usually is, a nil-backed record's is not)
+  mo_move(o.g_vals + uint64_t(ds) * o.g_value_size, nullptr, o.g_value_size, sub, lanes);
+  mo_move(o.g_snap + uint64_t(ds) * o.g_value_size, nullptr, o.g_value_size, sub, lanes);
+  if (sub != 0) return;
+  if (!(st & (XE_SLOT_FULL | XE_SLOT_TOMB))) {  // claimed free: the key words are the claiming slot's group key
+    uint64_t kw[XE_MAX_KEY / 8];
+    mg_group_key(o, uint32_t(w0 >> 32) - 1, kw);
+    for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
+      if (k < o.g_kwords) r[1 + k] = kw[k];
+  }
+  r[0] = XE_SLOT_FULL;
+}
+XE_HD void mg_publish_count(const XeMapOp& o) { *o.g_count += o.ctr[kMoNew]; }
+// ADD: the destination slot of source slot sbase + s's group, read-only (the kernel has a faster probe for
+// short records); kMoAbsent cannot happen after LOCATE and PUBLISH and is skipped.
+XE_HD uint32_t mg_slot_of(const XeMapOp& o, uint32_t s) {
+  uint64_t kw[XE_MAX_KEY / 8];
+  mg_group_key(o, o.sbase + s, kw);
+  if (o.g_kind == XE_DM_ARRAY) return kw[0] < o.g_max_entries ? uint32_t(kw[0]) : kMoAbsent;
+  return mo_find(mg_dst(o), kw);
+}
+// ... and `count` entries with measures summing to `sum` added to destination slot ds, in the map and in the
+// delta base alike (so xe_map_delta sees no packet adds).
+XE_HD void mg_add_item(const XeMapOp& o, uint32_t ds, uint64_t count, uint64_t sum) {
+  uint8_t* v = o.g_vals + uint64_t(ds) * o.g_value_size;
+  uint8_t* b = o.g_snap + uint64_t(ds) * o.g_value_size;
+  if (o.g_count_off != kMgNone) {
+    mo_add64(reinterpret_cast<uint64_t*>(v + o.g_count_off), count);
+    mo_add64(reinterpret_cast<uint64_t*>(b + o.g_count_off), count);
+  }
+  if (o.g_sum_off != kMgNone) {
+    mo_add64(reinterpret_cast<uint64_t*>(v + o.g_sum_off), sum);
+    mo_add64(reinterpret_cast<uint64_t*>(b + o.g_sum_off), sum);
+  }
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
@@ -672,6 +855,32 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
     XeMtStats a{};
     for (uint32_t s = 0; s < o.nslots; s++) mt_stats_item(o, s, &a);
     mt_stats_flush(o, a);
+    return 0;
+  }
+  if (step == XE_MO_GROUP_LOCATE || step == XE_MO_GROUP_ADD) {  // over the source bitmap
+    for (uint32_t t = 0; t < tiles; t++)
+      for (uint32_t r = 0; r < kMsRounds; r++) {
+        const uint64_t word = o.bitmap[uint64_t(t) * kMsRounds + r];
+        for (uint32_t lane = 0; lane < 64; lane++) {
+          if (!((word >> lane) & 1)) continue;
+          const uint32_t s = t * kMsTile + r * 64 + lane;
+          if (step == XE_MO_GROUP_LOCATE) {
+            if (mg_locate_item(o, s)) o.ctr[kMoNew]++;
+          } else {
+            const uint32_t ds = mg_slot_of(o, s);
+            if (ds != kMoAbsent) mg_add_item(o, ds, 1, mg_measure(o, o.sbase + s));
+          }
+        }
+      }
+    return 0;
+  }
+  if (step == XE_MO_GROUP_UNDO || step == XE_MO_GROUP_PUBLISH) {  // over the destination table
+    if (o.g_kind != XE_DM_HASH) return 0;
+    for (uint32_t ds = 0; ds < o.g_cap; ds++) {
+      if (step == XE_MO_GROUP_UNDO) mg_undo_item(o, ds);
+      else if (mg_claimed(o, ds)) mg_publish_item(o, ds, 0, 1);
+    }
+    if (step == XE_MO_GROUP_PUBLISH) mg_publish_count(o);
     return 0;
   }
   for (uint32_t i = 0; i < o.n; i++) {

@@ -1,4 +1,4 @@
-// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats (xe_mapops.h:
+// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group (xe_mapops.h:
 // the steps and what each one decides). One kernel per step; a step works either one batch entry per lane
 // (probes, claims, marks) or one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
 // destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
@@ -349,12 +349,117 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_stats_kernel(XeMapOp o, 
   }
 }
 
+// ---- group. LOCATE and ADD read the source bitmap a wave per tile (SCATTER's shape); UNDO and PUBLISH walk the
+// destination table a wave per tile (SELECT's shape). A lane's work is a probe of the destination, so the
+// rounds of a tile run one after another.
+__global__ void __launch_bounds__(kMoThreads) xe_mapgroup_locate_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint64_t word[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap[uint64_t(t) * kMsRounds + r];
+#pragma unroll 1
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      if (!word[r]) continue;
+      const bool fresh = ((word[r] >> lane) & 1) && mg_locate_item(o, t * kMsTile + r * 64 + lane);
+      const unsigned long long b = __ballot(fresh);  // the claims, counted once per wave
+      if (b && lane == uint32_t(__builtin_ctzll(b))) mo_add32(o.ctr + kMoNew, uint32_t(__popcll(b)));
+    }
+  }
+}
+
+// The read-only probe of ADD: find_slot's choice of walk, over the destination.
+__device__ __forceinline__ uint32_t group_slot(const XeMapOp& o, uint32_t s) {
+  if (o.g_kind == XE_DM_ARRAY) return mg_slot_of(o, s);
+  uint64_t kw[XE_MAX_KEY / 8];
+  mg_group_key(o, o.sbase + s, kw);
+  const XeMapOp d = mg_dst(o);
+  if (d.rwords == 2) return find_grouped<2>(d, kw);
+  if (d.rwords == 4) return find_grouped<4>(d, kw);
+  return mo_find(d, kw);
+}
+
+// ADD. A low-cardinality group-by sends most of a round's lanes to one or two destination slots, and many
+// adders on one address serialise in the L2. So, as xe_maptop_prefix_kernel does for its leader's bin, the
+// wave combines first: the first remaining lane leads, the lanes with its slot are balloted, their count is a
+// popcount and their measures a wave sum, the leader adds once for all of them; kMgLeaders times a round, the
+// lanes still left add singly.
+__global__ void __launch_bounds__(kMoThreads) xe_mapgroup_add_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  const bool measured = o.g_sum_off != kMgNone;
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint64_t word[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap[uint64_t(t) * kMsRounds + r];
+#pragma unroll 1
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      if (!word[r]) continue;
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      uint32_t ds = kMoAbsent;
+      uint64_t m = 0;
+      if ((word[r] >> lane) & 1) {
+        ds = group_slot(o, s);
+        if (measured) m = mg_measure(o, o.sbase + s);
+      }
+      bool left = ds != kMoAbsent;
+#pragma unroll 1
+      for (uint32_t l = 0; l < kMgLeaders; l++) {
+        const unsigned long long act = __ballot(left);
+        if (!act) break;
+        const uint32_t lead = uint32_t(__builtin_ctzll(act)), lds = uint32_t(__shfl(int(ds), int(lead), 64));
+        const bool mine = left && ds == lds;
+        const unsigned long long same = __ballot(mine);
+        uint64_t sum = mine ? m : 0;
+        if (measured) {
+#pragma unroll
+          for (uint32_t d = 32; d; d >>= 1) sum += __shfl_xor((unsigned long long)sum, int(d), 64);
+        }
+        if (lane == lead) mg_add_item(o, lds, uint64_t(__popcll(same)), sum);
+        left = left && !mine;
+      }
+      if (left) mg_add_item(o, ds, 1, m);
+    }
+  }
+}
+
+// UNDO / PUBLISH over the destination table. PUBLISH: a value of up to kMoInline bytes is zeroed by its record's
+// lane; a larger one by the whole wave, one claimed record of the round after another.
+__global__ void __launch_bounds__(kMoThreads) xe_mapgroup_dst_kernel(XeMapOp o, uint32_t tiles, uint32_t step) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  if (step == XE_MO_GROUP_PUBLISH && blockIdx.x == 0 && threadIdx.x == 0) mg_publish_count(o);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+#pragma unroll 1
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t ds = t * kMsTile + r * 64 + lane;
+      const bool in = ds < o.g_cap;
+      if (step == XE_MO_GROUP_UNDO) {
+        if (in) mg_undo_item(o, ds);
+        continue;
+      }
+      const bool claimed = in && mg_claimed(o, ds);
+      if (o.g_value_size <= kMoInline) {
+        if (claimed) mg_publish_item(o, ds, 0, 1);
+        continue;
+      }
+      unsigned long long todo = __ballot(claimed);
+      while (todo) {
+        const uint32_t l = uint32_t(__builtin_ctzll(todo));
+        todo &= todo - 1;
+        mg_publish_item(o, t * kMsTile + r * 64 + l, lane, 64);
+      }
+    }
+  }
+}
+
 }  // namespace
 
-// SELECT / SCATTER and the tile passes of top / evict / stats: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
+// SELECT / SCATTER and the tile passes of top / evict / stats / group: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
 // would take, between kMoOneTurn and kMoMaxBlocks (the file's policy), the waves striding over the tiles.
 static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
-  const uint32_t tiles = xe_ms_tiles(op->nslots);
+  // UNDO and PUBLISH walk the destination table, every other step the source's slots
+  const bool dst = step == XE_MO_GROUP_UNDO || step == XE_MO_GROUP_PUBLISH;
+  if (dst && op->g_kind != XE_DM_HASH) return 0;
+  const uint32_t tiles = xe_ms_tiles(dst ? op->g_cap : op->nslots);
   if (!tiles) return 0;
   if (step == XE_MO_SCAN_SCAN) {
     hipLaunchKernelGGL(xe_mapscan_scan_kernel, dim3(1), dim3(kMsScanThreads), 0, s, *op, tiles);
@@ -371,6 +476,9 @@ static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
   else if (step == XE_MO_TOP_CUT) hipLaunchKernelGGL(xe_maptop_cut_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   else if (step == XE_MO_TOP_TRIM) hipLaunchKernelGGL(xe_maptop_trim_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   else if (step == XE_MO_TOP_STATS) hipLaunchKernelGGL(xe_maptop_stats_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_GROUP_LOCATE) hipLaunchKernelGGL(xe_mapgroup_locate_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_GROUP_ADD) hipLaunchKernelGGL(xe_mapgroup_add_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (dst) hipLaunchKernelGGL(xe_mapgroup_dst_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles, step);
   else hipLaunchKernelGGL(xe_mapscan_scatter_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

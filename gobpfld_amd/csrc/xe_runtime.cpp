@@ -4291,9 +4291,8 @@ constexpr uint64_t kMoMaxCount = 1ull << 31;
 // Common start of the batched calls and of scan / expire: pipelined batches complete, the map is of a served
 // kind and current on the device, the per-entry scratch holds `count` slots behind zeroed counters. 1: nothing
 // to do (count 0).
-int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, HostMap** mp, XeMapOp* op, xe_stream_t* sp) {
-  if (!vm) return XE_ERR_INVAL;
-  if (int rc = xe_sync(vm)) return rc;
+// Its parts, which the group-by runs for two maps: the map is of a served kind and may be written; ...
+int mapop_map(xe_vm* vm, int32_t mi, bool writes, HostMap** mp) {
   HostMap* m = get_map(vm, mi);
   if (!m) return fail(vm, XE_ERR_INVAL, "map index out of bounds");
   if (m->ordered() || (m->dkind != XE_DM_ARRAY && m->dkind != XE_DM_HASH))
@@ -4301,16 +4300,28 @@ int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream
   if (m->dkind == XE_DM_ARRAY && m->def.max_entries >= kMoAbsent)
     return fail(vm, XE_ERR_UNSUPPORTED, "batched device map operations: ARRAY map too large");
   if (writes && vm->epoch_open) return fail(vm, XE_ERR_INVAL, "map writes are refused while a shard epoch is open");
+  *mp = m;
+  return XE_OK;
+}
+// ... and current on the device: a host-dirty map is uploaded once.
+int mapop_current(xe_vm* vm, HostMap* m) {
+  if (!m->host_dirty) return XE_OK;
+  vm->staged_slot = -1;  // the device values change under the staged snapshots
+  if (map_upload(vm, *m)) return fail(vm, XE_ERR_DEVICE, "map upload");
+  return XE_OK;
+}
+int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, HostMap** mp, XeMapOp* op, xe_stream_t* sp) {
+  if (!vm) return XE_ERR_INVAL;
+  if (int rc = xe_sync(vm)) return rc;
+  HostMap* m = nullptr;
+  if (int rc = mapop_map(vm, mi, writes, &m)) return rc;
   if (count > kMoMaxCount) return fail(vm, XE_ERR_INVAL, "batched map operation: more than 2^31 keys");
   if (set_device(vm->settings.device)) return fail(vm, XE_ERR_DEVICE, "hipSetDevice failed");
   xe_stream_t s = stream ? (xe_stream_t)stream : vm->stream;
   *mp = m;
   *sp = s;
   if (!count) return 1;
-  if (m->host_dirty) {
-    vm->staged_slot = -1;  // the device values change under the staged snapshots
-    if (map_upload(vm, *m)) return fail(vm, XE_ERR_DEVICE, "map upload");
-  }
+  if (int rc = mapop_current(vm, m)) return rc;
   if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(count) * 4) || dmemset(vm->d_mo, 0, kMoCounters * 4, s))
     return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
   XeMapOp o{};
@@ -4625,6 +4636,117 @@ static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe
   out->min = ~w[2];
   out->max = w[3];
   return XE_OK;
+}
+
+// Group (xe_mapops.h SELECT, SCAN on the source, then LOCATE .. ADD): the update's locate / undo / compact /
+// retry loop with the claims made by the source's selected slots. Nothing per entry is allocated.
+static int map_group_check(xe_vm* vm, const HostMap* sm, const HostMap* dm, const xe_map_group_spec* g) {
+  if (g->from > XE_MG_VALUE) return fail(vm, XE_ERR_INVAL, "map group: from must be XE_MG_KEY or XE_MG_VALUE");
+  if (g->pad) return fail(vm, XE_ERR_INVAL, "map group: pad must be 0");
+  const uint32_t src_key = sm->dkind == XE_DM_ARRAY ? 4 : sm->def.key_size;
+  if (uint64_t(g->offset) + g->len > (g->from == XE_MG_KEY ? src_key : sm->def.value_size))
+    return fail(vm, XE_ERR_INVAL, "map group: the group bytes lie outside the source key / value");
+  if (dm->dkind == XE_DM_HASH) {
+    if (!dm->def.key_size) return fail(vm, XE_ERR_INVAL, "map group: the destination has no key bytes");
+    if (g->len != dm->def.key_size) return fail(vm, XE_ERR_INVAL, "map group: len must be the destination's key_size");
+  } else if (g->len != 1 && g->len != 2 && g->len != 4) {
+    return fail(vm, XE_ERR_INVAL, "map group: len must be 1, 2 or 4 for an ARRAY destination");
+  }
+  if (g->count_off == XE_MG_NONE && g->sum_off == XE_MG_NONE) return fail(vm, XE_ERR_INVAL, "map group: no accumulator");
+  if (g->sum_off != XE_MG_NONE && !g->measure_width) return fail(vm, XE_ERR_INVAL, "map group: a sum needs a measure");
+  if (g->measure_width) {
+    if (g->measure_width != 1 && g->measure_width != 2 && g->measure_width != 4 && g->measure_width != 8)
+      return fail(vm, XE_ERR_INVAL, "map group: measure width must be 1, 2, 4 or 8");
+    if (uint64_t(g->measure_off) + g->measure_width > sm->def.value_size)
+      return fail(vm, XE_ERR_INVAL, "map group: the measure lies outside the source value");
+  }
+  if (dm->def.value_size & 7) return fail(vm, XE_ERR_INVAL, "map group: the destination's value_size must be a multiple of 8");
+  for (uint32_t off : {g->count_off, g->sum_off})
+    if (off != XE_MG_NONE && ((off & 7) || uint64_t(off) + 8 > dm->def.value_size))
+      return fail(vm, XE_ERR_INVAL, "map group: an accumulator must be 8-byte aligned inside the destination value");
+  if (g->count_off == g->sum_off) return fail(vm, XE_ERR_INVAL, "map group: the accumulators overlap");
+  return XE_OK;
+}
+static int map_group_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst, uint64_t* matched,
+                         uint64_t* created, void* stream) {
+  if (!vm) return XE_ERR_INVAL;
+  if (int rc = xe_sync(vm)) return rc;
+  HostMap *sm = nullptr, *dm = nullptr;
+  if (int rc = mapop_map(vm, src, false, &sm)) return rc;
+  if (int rc = mapop_map(vm, dst, true, &dm)) return rc;
+  if (!g) return fail(vm, XE_ERR_INVAL, "null map group spec");
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (src == dst) return fail(vm, XE_ERR_INVAL, "map group: source and destination are one map");
+  if (int rc = map_group_check(vm, sm, dm, g)) return rc;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  if (int rc = mapop_begin(vm, src, 1, false, stream, &sm, &o, &s)) return rc;  // (the counters; no per-entry slots)
+  if (int e = map_scan_setup(vm, sm, f, o)) return e;
+  if (int rc = mapop_current(vm, dm)) return rc;
+  *matched = 0;
+  if (created) *created = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return XE_OK;
+  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
+  o.bitmap = (uint64_t*)vm->d_ms;
+  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds);
+  const bool hash = dm->dkind == XE_DM_HASH;
+  o.g_kind = dm->dkind;
+  o.g_key_size = hash ? dm->def.key_size : 4;
+  o.g_value_size = dm->def.value_size;
+  o.g_max_entries = dm->def.max_entries;
+  o.g_cap = dm->cap;
+  o.g_kwords = dm->kwords;
+  o.g_rwords = hash ? xe_hash_rwords(dm->kwords) : 0;
+  o.g_from = g->from;
+  o.g_off = g->offset;
+  o.g_len = g->len;
+  o.g_moff = g->measure_off;
+  o.g_mwidth = g->measure_width;
+  o.g_count_off = g->count_off;
+  o.g_sum_off = g->sum_off;
+  o.g_recs = dm->d_keys;
+  o.g_vals = dm->d_vals;
+  o.g_snap = dm->d_snap;
+  o.g_count = dm->d_count;
+  if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
+  uint32_t total = 0;
+  if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
+  *matched = total;
+  if (!total) return XE_OK;
+  uint32_t ctr[kMoCounters], cnt = 0;
+  for (int attempt = 0;; attempt++) {
+    if (int r = mapop_steps(vm, o, {XE_MO_GROUP_LOCATE}, s)) return r;
+    if (d2h(ctr, o.ctr, sizeof ctr, s) || (hash && d2h(&cnt, dm->d_count, 4, s)) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
+    const bool range = ctr[kMoErr] & kMoErrRange, full = ctr[kMoErr] & kMoErrFull;
+    const bool fits = !hash || uint64_t(cnt) + ctr[kMoNew] <= dm->def.max_entries;
+    if (!range && !full && fits) break;
+    if (int r = mapop_steps(vm, o, {XE_MO_GROUP_UNDO}, s)) return r;
+    if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
+    if (hash) dm->dev_dirty = true;  // claims were written and put back: the mirror reads the device again
+    if (range) return fail(vm, XE_ERR_INVAL, "map group: a group's index is out of the destination's range");
+    if (!fits || attempt) return fail(vm, XE_ERR_NOMEM, "map group: the destination is full");
+    // the groups fit under max_entries but a probe chain has no free record left: one compaction through the
+    // host, as xe_map_update_batch_device makes it; the claims and the error are counted again
+    dm->dev_dirty = true;
+    vm->staged_slot = -1;
+    if (map_download(vm, *dm) || (dm->host_dirty && map_upload(vm, *dm))) return fail(vm, XE_ERR_DEVICE, "map compaction");
+    if (dmemset(o.ctr, 0, (kMoErr + 1) * 4, s)) return fail(vm, XE_ERR_DEVICE, "map group");
+  }
+  if (int r = mapop_steps(vm, o, {XE_MO_GROUP_PUBLISH, XE_MO_GROUP_ADD}, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
+  if (hash) {
+    dm->live = cnt + ctr[kMoNew];
+    if (created) *created = ctr[kMoNew];
+  }
+  dm->dev_dirty = true;
+  vm->staged_slot = -1;  // the device values changed under the staged snapshots
+  return XE_OK;
+}
+
+int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst_map, uint64_t* matched,
+                 uint64_t* created, void* stream) {
+  return map_group_run(vm, src_map, f, g, dst_map, matched, created, stream);
 }
 
 int xe_map_scan_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* d_keys, void* d_values, uint64_t cap_entries,

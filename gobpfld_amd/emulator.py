@@ -70,6 +70,24 @@ class MapOrder:
     descending: bool = True
 
 
+MG_KEY, MG_VALUE, MG_NONE = 0, 1, 0xffffffff  # XE_MG_* (include/xdpemu.h)
+
+
+@dataclass
+class MapGroup:
+    """xe_map_group_spec: group by the `len` bytes at byte `offset` of the source entry's key (`from_` MG_KEY;
+    an ARRAY source's index as a u32) or value (MG_VALUE); the destination's u64 at `count_off` gains the
+    group's entries, the one at `sum_off` the sum of their measures, `measure_width` bytes at `measure_off` of
+    the source value (VM.map_group). MG_NONE: no such accumulator."""
+    from_: int = MG_KEY
+    offset: int = 0
+    len: int = 4
+    count_off: int = 0
+    sum_off: int = MG_NONE
+    measure_off: int = 0
+    measure_width: int = 0
+
+
 @dataclass
 class Settings:
     max_steps: int = 1 << 20
@@ -449,6 +467,17 @@ class VM:
         out = N.MapStats()
         self._check(self.lib.map_stats(self.h, m, None if cf is None else C.byref(cf), C.byref(co), C.byref(out), None), "map stats")
         return {"count": out.count, "sum": out.sum, "min": out.min, "max": out.max}
+
+    def map_group(self, src: int, dst: int, group: "MapGroup", flt: "MapFilter | None" = None) -> tuple[int, int]:
+        """(matched, created): the entries of map `src` that `flt` selects, folded by `group` into the
+        accumulators of map `dst`'s entries on the device (xe_map_group); created: the new HASH entries."""
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        cg = N.MapGroup(group.from_, group.offset, group.len, group.measure_off, group.measure_width, group.count_off,
+                        group.sum_off, 0)
+        n, new = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.map_group(self.h, src, None if cf is None else C.byref(cf), C.byref(cg), dst, C.byref(n),
+                                       C.byref(new), None), "map group")
+        return int(n.value), int(new.value)
 
     def map_traffic(self, m: int) -> tuple[int, int]:
         """xe_debug_map_traffic: (uploads, downloads) of the whole map so far."""

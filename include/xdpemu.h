@@ -487,6 +487,52 @@ int xe_map_evict(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_ma
 int xe_map_stats(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_order* field,
                  struct xe_map_stats* out, void* stream);
 
+/* --- group-by on the device copy (ARRAY and HASH kinds, either side): the entries of one map that satisfy a
+ * filter are folded, by some bytes of their key or value, into the entries of another map of the same VM: a
+ * count and a sum per group, added to 64-bit accumulators in the destination's values. No entry crosses to
+ * the host. The rules of the scan block above hold unchanged for both maps (xe_sync first, one upload of a
+ * host-dirty map, finished on return, stream NULL is the VM's stream, the same four map types are
+ * XE_ERR_UNSUPPORTED on either side, the filter and its errors are the scan's).
+ *
+ *   folded:   the entries xe_map_scan_device would report for `f` on src_map; *matched = their number (NULL:
+ *             XE_ERR_INVAL). A nil-backed source value reads as zeros, for the group bytes and the measure.
+ *   group:    `len` bytes at byte `offset` of the source entry's key (ARRAY source: its index as a u32) or
+ *             value, any alignment. HASH destination: they are the destination key (len == its key_size).
+ *             ARRAY destination: len 1, 2 or 4, little endian, zero-extended: the index.
+ *   result:   every group that occurs gets a destination entry: an existing one keeps its other value bytes,
+ *             a created one starts all zero, a nil-backed one counts as all zero and stops being nil-backed.
+ *             The u64 at count_off of its value then gains the group's entries, the u64 at sum_off the sum of
+ *             their measures (modulo 2^64): the call adds to what the accumulators held, two calls accumulate.
+ *             *created (may be NULL) = the new HASH entries, 0 for an ARRAY destination. The source is only
+ *             read. The destination's delta base of xe_map_delta moves with its values; the call is refused
+ *             with XE_ERR_INVAL while a shard epoch is open.
+ *   failure:  the new groups do not fit under the destination's max_entries (after one compaction through the
+ *             host when tombstones have used up a probe chain, as xe_map_update_batch_device): XE_ERR_NOMEM.
+ *             An ARRAY index at or beyond max_entries: XE_ERR_INVAL. Both maps are then bit for bit what they
+ *             were.
+ *   errors:   g or matched NULL, src_map == dst_map, from > 1, pad != 0, group bytes outside the source key
+ *             (ARRAY: 4 bytes) or value, a len that does not fit the destination, a HASH destination with
+ *             key_size 0, both accumulators XE_MG_NONE, sum_off with measure_width 0, a measure width other
+ *             than 1, 2, 4 or 8 or a measure outside the source value, an accumulator that is not 8-byte
+ *             aligned or not inside the destination value, a destination value_size that is no multiple of 8,
+ *             count_off == sum_off: XE_ERR_INVAL, and nothing changes. */
+#define XE_MG_KEY 0     /* the group bytes are read from the source entry's key (ARRAY source: its u32 index) */
+#define XE_MG_VALUE 1   /* ... from the source entry's value */
+#define XE_MG_NONE 0xffffffffu
+typedef struct xe_map_group_spec {
+  uint32_t from;          /* XE_MG_KEY / XE_MG_VALUE */
+  uint32_t offset;        /* first group byte there; any alignment */
+  uint32_t len;           /* HASH destination: == its key_size (1..64). ARRAY destination: 1, 2 or 4; the bytes,
+                             little endian, zero-extended, are the index */
+  uint32_t measure_off;   /* the measure: `measure_width` bytes (1, 2, 4, 8) of the SOURCE value, as a filter's field */
+  uint32_t measure_width; /* 0: no measure */
+  uint32_t count_off;     /* byte offset in the DESTINATION value of a u64 that gains 1 per folded entry; XE_MG_NONE: none */
+  uint32_t sum_off;       /* ... of a u64 that gains the measure (mod 2^64); XE_MG_NONE: none */
+  uint32_t pad;           /* 0 */
+} xe_map_group_spec;
+int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst_map,
+                 uint64_t* matched, uint64_t* created, void* stream);
+
 /* --- one process, N devices (SURVEY §8b xe_run_batch_multi): the Go host shards a batch over the
  * GPUs of a node through the FFI alone. vms[k] runs on its own device with identical programs, maps
  * and map contents (the caller sets each up the same way). Exchange over RCCL (xGMI) when the devices
