@@ -86,6 +86,10 @@ class MapGroup(C.Structure):  # xe_map_group_spec
                 ("measure_width", C.c_uint32), ("count_off", C.c_uint32), ("sum_off", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class MapCompactInfo(C.Structure):  # xe_map_compact_info
+    _fields_ = [("tombstones", C.c_uint64), ("moved", C.c_uint64), ("longest_run", C.c_uint32), ("via_host", C.c_uint32)]
+
+
 # xe_helper_fn: int fn(void* user, uint32_t packet, const int64_t args[5], const uint8_t kinds[5], int64_t* r0)
 HELPER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8),
                         C.POINTER(C.c_int64))
@@ -180,6 +184,7 @@ _SIGS = {
     "map_evict": (C.c_int, [P, C.c_int32, P, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "map_stats": (C.c_int, [P, C.c_int32, P, P, P, P]),
     "map_group": (C.c_int, [P, C.c_int32, P, P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), P]),
+    "map_compact": (C.c_int, [P, C.c_int32, C.c_uint32, P, P]),
     "debug_map_traffic": (C.c_int, [P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "multi_create": (C.c_int, [P, C.c_uint32, C.POINTER(P)]),
     "multi_destroy": (None, [P]),
@@ -214,7 +219,7 @@ HEADER_SYMBOLS = [
     "xe_map_lookup_batch", "xe_map_update_batch_staged", "xe_map_delete_batch", "xe_debug_map_traffic",
     "xe_map_scan_device", "xe_map_expire_device", "xe_map_scan", "xe_map_expire",
     "xe_map_top_device", "xe_map_evict_device", "xe_map_top", "xe_map_evict", "xe_map_stats",
-    "xe_map_group",
+    "xe_map_group", "xe_map_compact",
     "xe_set_kernel_cache", "xe_kernel_source", "xe_compile_kernel_source", "xe_kernel_object_name",
     "xe_kernel_cache_stats",
     "xe_cancel", "xe_trace_config", "xe_trace_read", "xe_set_helper", "xe_reset_helper",

@@ -1,6 +1,6 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
 // xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device,
-// xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group): the per-key and per-slot decision logic that the kernels
+// xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group, xe_map_compact): the per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
 // declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
 //
@@ -77,6 +77,26 @@
 //                    then 64-bit atomic adds of the count and the measure into the map and the delta base.
 //                    The kernel combines the lanes of a wave that share a destination slot first, for up to
 //                    kMgLeaders distinct slots a round
+//   compact  MARK    the SELECT shape over the table's slots, word 0 of each record only: one ballot a round into
+//                    the first bitmap with the bit "free" (neither FULL nor a tombstone; the bits of slots past
+//                    the table are "not free"), one into the second with the bit "tombstone"; the tile counts
+//                    are the tombstones, the free records are counted in the counters (kMcFree)
+//            SCAN    (the scan's: the tombstones of the table, kMoMatched)
+//            REBUILD a tile pass: a run is a maximal sequence of consecutive non-free slots modulo cap; linear
+//                    probing never carries an entry across a free record, so every entry's home lies in its run
+//                    and the runs are independent. The lane whose slot is not free while its predecessor is (slot
+//                    0's is slot cap - 1) takes the run: its end and its first tombstone come from the two
+//                    bitmaps by word operations, no record of a clean run is read. A run with a tombstone is
+//                    rebuilt in place, front to back: the entry at run offset j probes from its home offset over
+//                    the records that are FULL now and stops at the first that is not, or at j; a target q < j
+//                    takes the record (VLEN0 kept, the high half zero) and the value (map and delta base), and
+//                    slot j is zeroed; a tombstone is zeroed, key words and values included. (home <= q <= j, and
+//                    the slots in front of j already hold the new layout: each of them was filled by an entry
+//                    that came earlier in run order, exactly the records an insertion in run order would have
+//                    met.) No atomics on the table: a run's writes stay inside it. A run with a tombstone that
+//                    is longer than kMcMaxRun is left alone and flagged (kMcLong): the runtime then compacts
+//                    through the host. The longest run with a tombstone is an atomic max; with c_only the pass
+//                    only measures
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
 // an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
@@ -87,9 +107,10 @@
 // keyed batch or by LOCATE, takes that record again, so a flow that is expired and learned again and again
 // keeps using one record instead of a fresh one each time; its value bytes are zero, as a reservation's are.
 // Clearing the words would turn every deleted record into a reservation for the all-zero key instead.
-// Tombstones of keys that never come back stay until the map next visits the host (drop_tombstones); when
-// they have used up a probe chain's free records LOCATE says so (kMoErrFull) and the runtime compacts the
-// table through the host once.
+// Tombstones of keys that never come back stay until xe_map_compact removes them on the device (MARK, REBUILD)
+// or the map next visits the host (drop_tombstones: the same layout for every run that does not wrap the
+// table's end); when they have used up a probe chain's free records LOCATE says so (kMoErrFull) and the
+// runtime compacts the table through the host once.
 #ifndef XE_MAPOPS_H
 #define XE_MAPOPS_H
 
@@ -102,6 +123,7 @@ enum : uint32_t {
   XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN, XE_MO_SCAN_SCATTER, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE,
   XE_MO_TOP_PREFIX, XE_MO_TOP_PICK, XE_MO_TOP_CUT, XE_MO_TOP_TRIM, XE_MO_TOP_STATS,
   XE_MO_GROUP_LOCATE, XE_MO_GROUP_UNDO, XE_MO_GROUP_PUBLISH, XE_MO_GROUP_ADD,
+  XE_MO_COMPACT_MARK, XE_MO_COMPACT_REBUILD,
   XE_MO_STEPS
 };
 
@@ -126,6 +148,10 @@ constexpr uint32_t kMsRounds = 4, kMsTile = 64 * kMsRounds, kMsScanThreads = 256
 #define XE_MG_LEADERS 4
 #endif
 constexpr uint32_t kMgLeaders = XE_MG_LEADERS, kMgNone = 0xffffffffu;
+// compact: the free records, the entries moved, the longest run with a tombstone, "a run with a tombstone is
+// longer than kMcMaxRun" (counters); kMcMaxRun bounds the records one lane walks alone (DESIGN.md has the walk's
+// measured time); kMcDead: the record at a run offset is no entry
+constexpr uint32_t kMcFree = 4, kMcMoved = 5, kMcLongest = 6, kMcLong = 7, kMcMaxRun = 4096, kMcDead = 0xffffffffu;
 // the filter's ops (include/xdpemu.h XE_MF_*)
 enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
 
@@ -166,6 +192,8 @@ struct XeMapOp {
   uint8_t* g_vals;
   uint8_t* g_snap;
   uint32_t* g_count;
+  // compact
+  uint32_t c_only;        // 1: REBUILD measures and changes nothing
 };
 inline uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
 
@@ -742,6 +770,87 @@ XE_HD void mg_add_item(const XeMapOp& o, uint32_t ds, uint64_t count, uint64_t s
   }
 }
 
+// ---------------------------------------------------------------- compact
+// MARK, slot s (< cap): 0 free, 1 a tombstone, 2 an entry.
+XE_HD uint32_t mc_mark_item(const XeMapOp& o, uint32_t s) {
+  const uint32_t st = uint32_t(o.recs[uint64_t(s) * o.rwords]);
+  return (st & XE_SLOT_FULL) ? 2u : (st & XE_SLOT_TOMB) ? 1u : 0u;
+}
+// One bit of a bitmap: slot s sits in word s / 64 (tile s / kMsTile, round s / 64 % kMsRounds).
+XE_HD bool mc_bit(const uint64_t* bm, uint32_t s) { return (bm[s >> 6] >> (s & 63)) & 1; }
+// REBUILD: does slot s (< cap) start a run? It is not free and its predecessor modulo cap is.
+XE_HD bool mc_run_start(const XeMapOp& o, uint32_t s) {
+  return !mc_bit(o.bitmap, s) && mc_bit(o.bitmap, (s - 1) & (o.cap - 1));
+}
+// ... and the run that starts there: its slots up to the next free one (through the table's end), and the
+// offset of its first tombstone (>= the length: none). Word operations on the two bitmaps; a run has a start
+// only when the table has a free record, so the walk ends.
+XE_HD uint32_t mc_run_scan(const XeMapOp& o, uint32_t s, uint32_t* first_tomb) {
+  uint32_t len = 0, first = 0xffffffffu, p = s;
+  while (len < o.cap) {
+    const uint32_t bit = p & 63, left = o.cap - p;
+    const uint32_t valid = 64 - bit < left ? 64 - bit : left;  // slots of this word from p on, inside the table
+    const uint64_t in = valid == 64 ? ~uint64_t(0) : (uint64_t(1) << valid) - 1;
+    const uint64_t fr = (o.bitmap[p >> 6] >> bit) & in;
+    uint64_t tb = (o.bitmap2[p >> 6] >> bit) & in;
+    const uint32_t upto = fr ? uint32_t(__builtin_ctzll(fr)) : valid;
+    if (upto < 64) tb &= (uint64_t(1) << upto) - 1;
+    if (tb && first == 0xffffffffu) first = len + uint32_t(__builtin_ctzll(tb));
+    len += upto;
+    if (fr) break;
+    p = (p + valid) & (o.cap - 1);
+  }
+  *first_tomb = first;
+  return len;
+}
+// The walk, run offset j of the run that starts at slot s (every slot in front of j holds the new layout):
+// the offset the entry there belongs at (j: it stays), kMcDead when the record is no entry. An entry whose home
+// lay outside the slots in front of it (no table the map's calls make) stays.
+XE_HD uint32_t mc_target(const XeMapOp& o, uint32_t s, uint32_t j) {
+  const uint32_t mask = o.cap - 1;
+  const uint64_t* r = o.recs + uint64_t((s + j) & mask) * o.rwords;
+  if (!(uint32_t(r[0]) & XE_SLOT_FULL)) return kMcDead;
+  uint32_t q = (uint32_t(xe_hash_words(r + 1, o.kwords, o.key_size)) - s) & mask;
+  if (q > j) return j;
+  while (q < j && (uint32_t(o.recs[uint64_t((s + q) & mask) * o.rwords]) & XE_SLOT_FULL)) q++;
+  return q;
+}
+// ... and what follows from it, by lane `sub` of the `lanes` that share the record: the record and the value
+// (map and delta base) move to offset q < j and slot j is zeroed; a record that is no entry is zeroed.
+XE_HD void mc_apply(const XeMapOp& o, uint32_t s, uint32_t j, uint32_t q, uint32_t sub, uint32_t lanes) {
+  if (q == j) return;
+  const uint32_t mask = o.cap - 1, at = (s + j) & mask;
+  uint64_t* r = o.recs + uint64_t(at) * o.rwords;
+  uint8_t* v = o.vals + uint64_t(at) * o.value_size;
+  uint8_t* b = o.snap + uint64_t(at) * o.value_size;
+  if (q != kMcDead) {
+    const uint32_t to = (s + q) & mask;
+    mo_move(o.vals + uint64_t(to) * o.value_size, v, o.value_size, sub, lanes);
+    mo_move(o.snap + uint64_t(to) * o.value_size, b, o.value_size, sub, lanes);
+    if (sub == 0) {
+      uint64_t* t = o.recs + uint64_t(to) * o.rwords;
+      for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
+        if (k < o.kwords) t[1 + k] = r[1 + k];
+      t[0] = uint64_t(uint32_t(r[0]) & (XE_SLOT_FULL | XE_SLOT_VLEN0));
+    }
+  }
+  mo_move(v, nullptr, o.value_size, sub, lanes);
+  mo_move(b, nullptr, o.value_size, sub, lanes);
+  if (sub == 0) {
+    for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
+      if (k < o.kwords) r[1 + k] = 0;
+    r[0] = 0;
+  }
+}
+// What a run of len slots whose first tombstone is at offset `first` adds to the counters; true: it is to be
+// rebuilt (the walk starts at `first`: the entries in front of the first tombstone never move).
+XE_HD bool mc_run_counts(const XeMapOp& o, uint32_t len, uint32_t first) {
+  if (first >= len) return false;
+  mo_max32(o.ctr + kMcLongest, len);
+  if (len > kMcMaxRun) { mo_or32(o.ctr + kMcLong, 1); return false; }
+  return !o.c_only;
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
@@ -881,6 +990,40 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
       else if (mg_claimed(o, ds)) mg_publish_item(o, ds, 0, 1);
     }
     if (step == XE_MO_GROUP_PUBLISH) mg_publish_count(o);
+    return 0;
+  }
+  if (step == XE_MO_COMPACT_MARK) {
+    for (uint32_t t = 0; t < tiles; t++) {
+      uint32_t tombs = 0;
+      for (uint32_t r = 0; r < kMsRounds; r++) {
+        uint64_t fr = 0, tb = 0;
+        for (uint32_t lane = 0; lane < 64; lane++) {
+          const uint32_t s = t * kMsTile + r * 64 + lane;
+          const uint32_t c = s < o.nslots ? mc_mark_item(o, s) : 2;
+          if (c == 0) fr |= uint64_t(1) << lane;
+          if (c == 1) tb |= uint64_t(1) << lane;
+        }
+        o.bitmap[uint64_t(t) * kMsRounds + r] = fr;
+        o.bitmap2[uint64_t(t) * kMsRounds + r] = tb;
+        tombs += uint32_t(__builtin_popcountll(tb));
+        o.ctr[kMcFree] += uint32_t(__builtin_popcountll(fr));
+      }
+      o.tile[t] = tombs;
+    }
+    return 0;
+  }
+  if (step == XE_MO_COMPACT_REBUILD) {
+    for (uint32_t s = 0; s < o.nslots; s++) {
+      if (!mc_run_start(o, s)) continue;
+      uint32_t first = 0;
+      const uint32_t len = mc_run_scan(o, s, &first);
+      if (!mc_run_counts(o, len, first)) continue;
+      for (uint32_t j = first; j < len; j++) {
+        const uint32_t q = mc_target(o, s, j);
+        if (q < j) o.ctr[kMcMoved]++;
+        mc_apply(o, s, j, q, 0, 1);
+      }
+    }
     return 0;
   }
   for (uint32_t i = 0; i < o.n; i++) {

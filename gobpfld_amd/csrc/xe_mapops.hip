@@ -1,4 +1,4 @@
-// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group (xe_mapops.h:
+// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group, compact (xe_mapops.h:
 // the steps and what each one decides). One kernel per step; a step works either one batch entry per lane
 // (probes, claims, marks) or one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
 // destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
@@ -451,6 +451,81 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapgroup_dst_kernel(XeMapOp o, 
   }
 }
 
+// ---- compact. MARK has SELECT's shape and reads word 0 of every record once: two ballots a round, the tile's
+// tombstones for SCAN, the tile's free records in one atomic.
+__global__ void __launch_bounds__(kMoThreads) xe_mapcompact_mark_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+    uint32_t c[kMsRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      c[r] = s < o.nslots ? mc_mark_item(o, s) : 2;
+    }
+    uint32_t tombs = 0, frees = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const unsigned long long fr = __ballot(c[r] == 0), tb = __ballot(c[r] == 1);
+      if (lane == 0) {
+        o.bitmap[uint64_t(t) * kMsRounds + r] = fr;
+        o.bitmap2[uint64_t(t) * kMsRounds + r] = tb;
+      }
+      frees += uint32_t(__popcll(fr));
+      tombs += uint32_t(__popcll(tb));
+    }
+    if (lane == 0) {
+      o.tile[t] = tombs;
+      if (frees) mo_add32(o.ctr + kMcFree, frees);
+    }
+  }
+}
+
+// REBUILD: a lane whose slot starts a run measures it from the bitmaps. Values of up to kMoInline bytes: the lane
+// walks its run alone. Larger values: the wave takes the runs of the round one after another, as PUBLISH takes
+// its records: lane 0 decides where each record goes, every lane moves its share of the value.
+__global__ void __launch_bounds__(kMoThreads) xe_mapcompact_rebuild_kernel(XeMapOp o, uint32_t tiles) {
+  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+#pragma unroll 1
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      uint32_t len = 0, first = 0, moved = 0;
+      bool mine = false;
+      if (s < o.nslots && mc_run_start(o, s)) {
+        len = mc_run_scan(o, s, &first);
+        mine = mc_run_counts(o, len, first);
+      }
+      unsigned long long todo = __ballot(mine);
+      if (!todo) continue;
+      if (o.value_size <= kMoInline) {
+        if (mine) {
+          for (uint32_t j = first; j < len; j++) {
+            const uint32_t q = mc_target(o, s, j);
+            moved += q < j;
+            mc_apply(o, s, j, q, 0, 1);
+          }
+        }
+      } else {
+        while (todo) {
+          const int l = __builtin_ctzll(todo);
+          todo &= todo - 1;
+          const uint32_t rs = uint32_t(__shfl(int(s), l, 64)), rlen = uint32_t(__shfl(int(len), l, 64));
+#pragma unroll 1
+          for (uint32_t j = uint32_t(__shfl(int(first), l, 64)); j < rlen; j++) {
+            const uint32_t q = uint32_t(__shfl(int(lane == 0 ? mc_target(o, rs, j) : 0u), 0, 64));
+            moved += lane == 0 && q < j;
+            mc_apply(o, rs, j, q, lane, 64);
+          }
+        }
+      }
+      // the entries moved, counted once per wave
+#pragma unroll
+      for (uint32_t d = 32; d; d >>= 1) moved += uint32_t(__shfl_xor(int(moved), int(d), 64));
+      if (lane == 0 && moved) mo_add32(o.ctr + kMcMoved, moved);
+    }
+  }
+}
+
 }  // namespace
 
 // SELECT / SCATTER and the tile passes of top / evict / stats / group: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
@@ -478,6 +553,8 @@ static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
   else if (step == XE_MO_TOP_STATS) hipLaunchKernelGGL(xe_maptop_stats_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   else if (step == XE_MO_GROUP_LOCATE) hipLaunchKernelGGL(xe_mapgroup_locate_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   else if (step == XE_MO_GROUP_ADD) hipLaunchKernelGGL(xe_mapgroup_add_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_COMPACT_MARK) hipLaunchKernelGGL(xe_mapcompact_mark_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
+  else if (step == XE_MO_COMPACT_REBUILD) hipLaunchKernelGGL(xe_mapcompact_rebuild_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   else if (dst) hipLaunchKernelGGL(xe_mapgroup_dst_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles, step);
   else hipLaunchKernelGGL(xe_mapscan_scatter_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
   return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -4749,6 +4749,54 @@ int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_ma
   return map_group_run(vm, src_map, f, g, dst_map, matched, created, stream);
 }
 
+// Compact (xe_mapops.h MARK, SCAN, REBUILD): the counters are read after SCAN (no tombstone: nothing is
+// written; no free record: no run has a start) and after REBUILD (a run too long for one lane). Both of these
+// tables take the route through the host mirror that xe_map_update_batch_device takes for a full probe chain.
+int xe_map_compact(xe_vm* vm, int32_t mi, uint32_t flags, xe_map_compact_info* info, void* stream) {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+  const bool only = flags & XE_MC_COUNT_ONLY;
+  const int rc = mapop_begin(vm, mi, 1, !only, stream, &m, &o, &s);  // (the counters)
+  if (rc < 0) return rc;
+  if (!info) return fail(vm, XE_ERR_INVAL, "null compact info");
+  if (flags & ~XE_MC_COUNT_ONLY) return fail(vm, XE_ERR_INVAL, "map compact: unknown flag");
+  *info = xe_map_compact_info{};
+  if (m->dkind != XE_DM_HASH) return XE_OK;  // an ARRAY has no tombstones
+  o.nslots = m->cap;
+  o.c_only = only;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * 2 * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
+  o.bitmap = (uint64_t*)vm->d_ms;
+  o.bitmap2 = o.bitmap + tiles * kMsRounds;
+  o.tile = (uint32_t*)(o.bitmap2 + tiles * kMsRounds);
+  o.tile2 = o.tile + tiles;
+  if (int r = mapop_steps(vm, o, {XE_MO_COMPACT_MARK, XE_MO_SCAN_SCAN}, s)) return r;
+  uint32_t ctr[kMoCounters];
+  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map compact");
+  info->tombstones = ctr[kMoMatched];
+  if (!ctr[kMoMatched]) return XE_OK;
+  bool host = !ctr[kMcFree];
+  if (host) {
+    info->longest_run = m->cap;
+  } else {
+    if (int r = mapop_steps(vm, o, {XE_MO_COMPACT_REBUILD}, s)) return r;
+    if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map compact");
+    info->longest_run = ctr[kMcLongest];
+    host = ctr[kMcLong] != 0;
+  }
+  if (only) return XE_OK;
+  m->dev_dirty = true;
+  vm->staged_slot = -1;  // the device values moved under the staged snapshots
+  if (host) {
+    if (map_download(vm, *m) || (m->host_dirty && map_upload(vm, *m))) return fail(vm, XE_ERR_DEVICE, "map compaction");
+    info->via_host = 1;
+  } else {
+    info->moved = ctr[kMcMoved];
+  }
+  return XE_OK;
+}
+
 int xe_map_scan_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* d_keys, void* d_values, uint64_t cap_entries,
                        uint64_t* matched, void* stream) {
   return map_scan_run(vm, mi, f, d_keys, d_values, cap_entries, matched, stream, false, false);

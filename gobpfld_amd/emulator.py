@@ -71,6 +71,7 @@ class MapOrder:
 
 
 MG_KEY, MG_VALUE, MG_NONE = 0, 1, 0xffffffff  # XE_MG_* (include/xdpemu.h)
+MC_COUNT_ONLY = 1  # XE_MC_COUNT_ONLY
 
 
 @dataclass
@@ -478,6 +479,14 @@ class VM:
         self._check(self.lib.map_group(self.h, src, None if cf is None else C.byref(cf), C.byref(cg), dst, C.byref(n),
                                        C.byref(new), None), "map group")
         return int(n.value), int(new.value)
+
+    def map_compact(self, m: int, count_only: bool = False) -> dict:
+        """{tombstones, moved, longest_run, via_host}: every tombstone of HASH map `m` removed on the device
+        copy, the live entries moved to where linear probing wants them (xe_map_compact). count_only:
+        measure and change nothing."""
+        info = N.MapCompactInfo()
+        self._check(self.lib.map_compact(self.h, m, MC_COUNT_ONLY if count_only else 0, C.byref(info), None), "map compact")
+        return {"tombstones": info.tombstones, "moved": info.moved, "longest_run": info.longest_run, "via_host": info.via_host}
 
     def map_traffic(self, m: int) -> tuple[int, int]:
         """xe_debug_map_traffic: (uploads, downloads) of the whole map so far."""

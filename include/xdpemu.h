@@ -533,6 +533,41 @@ typedef struct xe_map_group_spec {
 int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst_map,
                  uint64_t* matched, uint64_t* created, void* stream);
 
+/* --- tombstone compaction on the device copy (HASH maps). The removing calls above (xe_map_delete_batch_device,
+ * xe_map_expire*, xe_map_evict*) and the keyed path's unused reservations leave tombstones that keep their key
+ * words, and every probe walks through them. xe_map_compact removes every tombstone of the table in place and
+ * moves the live entries to where linear probing wants them. Nothing of the map crosses to the host. The rules
+ * of the scan block above hold unchanged (xe_sync first, one upload of a host-dirty map, which then has no
+ * tombstones; finished on return; stream NULL is the VM's stream; LRU_HASH, QUEUE, STACK and PERF_EVENT_ARRAY
+ * are XE_ERR_UNSUPPORTED). An ARRAY map has no tombstones: XE_OK with an all-zero info.
+ *
+ *   result:   a run is a maximal sequence of consecutive records (modulo the table size) that are entries or
+ *             tombstones, bounded by free records. No entry's probe chain crosses a free record, so the runs
+ *             are independent. Every run that holds a tombstone is replaced by what clearing it and inserting
+ *             its entries again, in run order (from the run's first slot onwards, through the end of the table
+ *             for the one run that may wrap), gives. An entry keeps its key, its value (in the delta base of
+ *             xe_map_delta too: per-key deltas do not change) and its nil-backed mark; every record that is
+ *             no entry afterwards is all zero, key words, value and delta base included. The entry count does
+ *             not change. For every run that does not wrap this is bit for bit the layout a host visit
+ *             (xe_map_dump, ...) leaves; the wrapping run occupies the same records as after a host visit but
+ *             may arrange its entries differently (the host inserts from slot 0). The result is a function of
+ *             the map's state alone: two VMs in the same state compact to identical bytes.
+ *   via_host: when the table holds tombstones and no free record at all, or a run with a tombstone is longer
+ *             than the 4,096 records one lane walks, the table is compacted through the host mirror instead,
+ *             once (one download and one upload of the map); via_host = 1 and moved = 0.
+ *   flags:    XE_MC_COUNT_ONLY measures (tombstones, longest_run) and changes nothing.
+ *   errors:   info NULL or an unknown flag bit: XE_ERR_INVAL. While a shard epoch is open the call is
+ *             refused with XE_ERR_INVAL unless XE_MC_COUNT_ONLY is set. */
+#define XE_MC_COUNT_ONLY 1u   /* measure, change nothing */
+typedef struct xe_map_compact_info {
+  uint64_t tombstones;   /* tombstones in the table when the call began */
+  uint64_t moved;        /* live entries that changed slot (0 under XE_MC_COUNT_ONLY or via_host) */
+  uint32_t longest_run;  /* slots of the longest run that holds a tombstone (the table size when it has no
+                            free record); 0: none */
+  uint32_t via_host;     /* 1: the table was compacted through the host mirror */
+} xe_map_compact_info;
+int xe_map_compact(xe_vm* vm, int32_t map_idx, uint32_t flags, xe_map_compact_info* info, void* stream);
+
 /* --- one process, N devices (SURVEY §8b xe_run_batch_multi): the Go host shards a batch over the
  * GPUs of a node through the FFI alone. vms[k] runs on its own device with identical programs, maps
  * and map contents (the caller sets each up the same way). Exchange over RCCL (xGMI) when the devices
