@@ -155,14 +155,17 @@ constexpr uint32_t kMcFree = 4, kMcMoved = 5, kMcLongest = 6, kMcLong = 7, kMcMa
 // the filter's ops (include/xdpemu.h XE_MF_*)
 enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
 
-struct XeMapOp {
+// One table: what a probe reads. A call's source map is the XeMapOp itself, the group's destination its `dst`.
+struct XeMapView {
   uint32_t kind;  // XE_DM_ARRAY / XE_DM_HASH
   uint32_t key_size, value_size, max_entries, cap, kwords, rwords;
-  uint32_t n;             // batch entries
   uint64_t* recs;         // HASH: slot records
   uint8_t* vals;
   uint8_t* snap;          // the delta base (HostMap::d_snap): kept equal to vals on the slots a call writes
   uint32_t* count;        // HASH: entry count
+};
+struct XeMapOp : XeMapView {
+  uint32_t n;             // batch entries
   uint32_t* win;          // ARRAY: last-writer word per index
   const uint8_t* keys;    // n x key_size (ARRAY: n x 4)
   const uint8_t* values_in;
@@ -183,19 +186,15 @@ struct XeMapOp {
   uint32_t* bins;         // [kMtBins] zero between the passes
   uint64_t* bitmap2;      // [tiles x kMsRounds] key == cut
   uint32_t* tile2;        // [tiles] equals per tile (CUT), then the equals in front of the tile (SCAN)
-  // group: the destination map beside the source above (mg_dst makes an XeMapOp of it for the probes)
-  uint32_t g_kind, g_key_size, g_value_size, g_max_entries, g_cap, g_kwords, g_rwords;
+  // group: the destination map beside the source above
+  XeMapView dst;
   uint32_t g_from, g_off, g_len;     // the group bytes: 0 the source key / 1 the source value, first byte, number
   uint32_t g_moff, g_mwidth;         // the measure in the source value (width 0: none)
   uint32_t g_count_off, g_sum_off;   // the accumulators in the destination value (kMgNone: none)
-  uint64_t* g_recs;
-  uint8_t* g_vals;
-  uint8_t* g_snap;
-  uint32_t* g_count;
   // compact
   uint32_t c_only;        // 1: REBUILD measures and changes nothing
 };
-inline uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
+XE_HD uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
 
 // lanes that share one value (a power of two <= 64)
 inline uint32_t xe_mo_lanes(uint32_t value_size) {
@@ -263,10 +262,15 @@ XE_HD uint32_t mo_load_index(const XeMapOp& o, uint32_t i) {
   const uint8_t* k = o.keys + uint64_t(i) * 4;
   return uint32_t(k[0]) | uint32_t(k[1]) << 8 | uint32_t(k[2]) << 16 | uint32_t(k[3]) << 24;
 }
-XE_HD bool mo_key_eq(const XeMapOp& o, const uint64_t* r, const uint64_t* kw) {
+XE_HD bool mo_key_eq(const XeMapView& o, const uint64_t* r, const uint64_t* kw) {
   bool eq = true;
   for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
     if (k < o.kwords) eq = eq && r[1 + k] == kw[k];
+  return eq;
+}
+XE_HD bool mo_words_eq(const uint64_t* a, const uint64_t* b) {  // two keys as mo_load_key pads them
+  bool eq = true;
+  for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++) eq = eq && a[k] == b[k];
   return eq;
 }
 // The last-writer word of a slot: the high half of a HASH record's word 0 (little endian), an ARRAY map's
@@ -292,7 +296,7 @@ XE_HD void mo_hi_max(const XeMapOp& o, uint32_t slot, uint32_t v) {
 
 // The walk of xe_interp.h hash_find, one record at a time: first record that is FULL and holds the key;
 // the chain ends at a record that is neither FULL nor a tombstone. kMoAbsent: not there.
-XE_HD uint32_t mo_find(const XeMapOp& o, const uint64_t* kw) {
+XE_HD uint32_t mo_find(const XeMapView& o, const uint64_t* kw) {
   if (o.key_size == 0) return (uint32_t(o.recs[uint64_t(o.cap) * o.rwords]) & XE_SLOT_FULL) ? o.cap : kMoAbsent;
   const uint32_t mask = o.cap - 1;
   uint32_t idx = uint32_t(xe_hash_words(kw, o.kwords, o.key_size)) & mask;
@@ -335,15 +339,16 @@ XE_HD void mo_move(uint8_t* t, const uint8_t* s, uint32_t len, uint32_t sub, uin
 }
 
 // ---------------------------------------------------------------- lookup / delete: find
-// Entry i's slot, read-only (kMoAbsent: absent or out of range).
-XE_HD uint32_t mo_slot_of(const XeMapOp& o, uint32_t i) {
+// Entry i's slot, read-only (kMoAbsent: absent or out of range). find: mo_find, or the kernels' faster probe.
+template <class Find>
+XE_HD uint32_t mo_slot_of(const XeMapOp& o, uint32_t i, Find find) {
   if (o.kind == XE_DM_ARRAY) {
     const uint32_t idx = mo_load_index(o, i);
     return idx < o.max_entries ? idx : kMoAbsent;
   }
   uint64_t kw[XE_MAX_KEY / 8];
   mo_load_key(o, i, kw);
-  return mo_find(o, kw);
+  return find(o, kw);
 }
 // ... and what follows from it: found[i], slot[i], and a small value on the same lane.
 XE_HD void mo_find_finish(const XeMapOp& o, uint32_t i, uint32_t s, bool with_value) {
@@ -363,8 +368,47 @@ XE_HD void mo_lookup_value_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint
 }
 
 // ---------------------------------------------------------------- update
-// Entry i's record: the one holding its key, or one claimed for it (see the head of this file). True: this
-// entry made the claim (the caller counts them). No free record: kMoErrFull.
+// The claim walk of update LOCATE and group LOCATE over HASH table v (see the head of this file): the record
+// that holds the key kw, or one claimed for it with word 0 `own` (BUSY | the claimer's name << 32). A record
+// claimed in this launch names its claimer j = (w0 >> 32) - 1: same(j) says whether j is a claimer with this
+// key. kEmptyKey: the table may be the empty key's one record past cap. kNilBacked: a FULL nil-backed record of
+// the key is claimed too, so that it can be zeroed. The slot, with kMoFresh when a free or a tombstone record
+// was claimed; kMoAbsent: no free record in the chain.
+template <bool kEmptyKey, bool kNilBacked, class Same>
+XE_HD uint32_t mo_claim_walk(const XeMapView& v, const uint64_t* kw, uint64_t own, Same same) {
+  const bool single = kEmptyKey && v.key_size == 0;
+  const uint32_t mask = v.cap - 1;
+  uint32_t idx = single ? v.cap : uint32_t(xe_hash_words(kw, v.kwords, v.key_size)) & mask;
+  for (uint32_t probe = 0; probe < v.cap;) {
+    uint64_t* r = v.recs + uint64_t(idx) * v.rwords;
+    const uint64_t w0 = mo_load64(r);
+    const uint32_t st = uint32_t(w0);
+    if (st & XE_SLOT_FULL) {
+      if (mo_key_eq(v, r, kw)) {
+        if (!kNilBacked || !(st & XE_SLOT_VLEN0) || (st & XE_SLOT_BUSY)) return idx;
+        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) return idx;
+        continue;  // lost it (to another claimer of this key): look again
+      }
+    } else if (st & XE_SLOT_TOMB) {  // holds key words: a deleted entry or an unused reservation
+      if (mo_key_eq(v, r, kw)) {
+        if (st & XE_SLOT_BUSY) return idx;  // a repetition of this key claimed it
+        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) return idx | kMoFresh;
+        continue;  // lost it (to a repetition of this key): look again
+      }
+    } else if (st & XE_SLOT_BUSY) {  // claimed in this launch by the claimer it names
+      if (same(uint32_t(w0 >> 32) - 1)) return idx;
+    } else {  // free
+      if (mo_cas64(r, w0, own) == w0) return idx | kMoFresh;
+      continue;  // lost it: look again
+    }
+    if (single) break;
+    idx = (idx + 1) & mask;
+    probe++;
+  }
+  return kMoAbsent;
+}
+// Entry i's record: the one holding its key, or one claimed for it. True: this entry made the claim (the
+// caller counts them). No free record: kMoErrFull.
 XE_HD bool mo_update_locate_item(const XeMapOp& o, uint32_t i) {
   if (o.kind == XE_DM_ARRAY) {
     const uint32_t idx = mo_load_index(o, i);
@@ -374,42 +418,15 @@ XE_HD bool mo_update_locate_item(const XeMapOp& o, uint32_t i) {
   }
   uint64_t kw[XE_MAX_KEY / 8];
   mo_load_key(o, i, kw);
-  const uint64_t own = XE_SLOT_BUSY | ((uint64_t(i) + 1) << 32);
-  const bool single = o.key_size == 0;  // the empty key: the one record past the table
-  const uint32_t mask = o.cap - 1;
-  uint32_t idx = single ? o.cap : uint32_t(xe_hash_words(kw, o.kwords, o.key_size)) & mask;
-  for (uint32_t probe = 0; probe < o.cap;) {
-    uint64_t* r = o.recs + uint64_t(idx) * o.rwords;
-    const uint64_t w0 = mo_load64(r);
-    const uint32_t st = uint32_t(w0);
-    if (st & XE_SLOT_FULL) {
-      if (mo_key_eq(o, r, kw)) { o.slot[i] = idx; return false; }
-    } else if (st & XE_SLOT_TOMB) {  // holds key words: a deleted entry or an unused reservation
-      if (mo_key_eq(o, r, kw)) {
-        if (st & XE_SLOT_BUSY) { o.slot[i] = idx; return false; }  // a repetition of this key claimed it
-        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) { o.slot[i] = idx | kMoFresh; return true; }
-        continue;  // lost it (to a repetition of this key): look again
-      }
-    } else if (st & XE_SLOT_BUSY) {  // claimed in this launch by the batch entry it names
-      uint64_t kj[XE_MAX_KEY / 8];
-      const uint32_t j = uint32_t(w0 >> 32) - 1;
-      bool eq = j < o.n;
-      if (eq) {
-        mo_load_key(o, j, kj);
-        for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++) eq = eq && kj[k] == kw[k];
-      }
-      if (eq) { o.slot[i] = idx; return false; }
-    } else {  // free
-      if (mo_cas64(r, w0, own) == w0) { o.slot[i] = idx | kMoFresh; return true; }
-      continue;  // lost it: look again
-    }
-    if (single) break;
-    idx = (idx + 1) & mask;
-    probe++;
-  }
-  mo_or32(o.ctr + kMoErr, kMoErrFull);
-  o.slot[i] = kMoAbsent;
-  return false;
+  const uint32_t c = mo_claim_walk<true, false>(o, kw, XE_SLOT_BUSY | ((uint64_t(i) + 1) << 32), [&](uint32_t j) {
+    uint64_t kj[XE_MAX_KEY / 8];
+    if (j >= o.n) return false;
+    mo_load_key(o, j, kj);
+    return mo_words_eq(kj, kw);
+  });
+  if (c == kMoAbsent) mo_or32(o.ctr + kMoErr, kMoErrFull);
+  o.slot[i] = c;
+  return (c & kMoFresh) != 0;
 }
 // The claim of entry i put back: a free record is free again (its key words were never written), a
 // tombstone is the tombstone it was.
@@ -623,23 +640,6 @@ XE_HD void mt_stats_flush(const XeMapOp& o, const XeMtStats& a) {
 }
 
 // ---------------------------------------------------------------- group
-// The destination as an XeMapOp of its own: what mo_find and mo_key_eq read.
-XE_HD XeMapOp mg_dst(const XeMapOp& o) {
-  XeMapOp d{};
-  d.kind = o.g_kind;
-  d.key_size = o.g_key_size;
-  d.value_size = o.g_value_size;
-  d.max_entries = o.g_max_entries;
-  d.cap = o.g_cap;
-  d.kwords = o.g_kwords;
-  d.rwords = o.g_rwords;
-  d.recs = o.g_recs;
-  d.vals = o.g_vals;
-  d.snap = o.g_snap;
-  d.count = o.g_count;
-  d.ctr = o.ctr;
-  return d;
-}
 // Is the value of source slot `at` nil-backed (it then reads as zeros)?
 XE_HD bool mg_src_zero(const XeMapOp& o, uint32_t at) {
   return o.kind == XE_DM_HASH && (uint32_t(o.recs[uint64_t(at) * o.rwords]) & XE_SLOT_VLEN0) != 0;
@@ -672,94 +672,65 @@ XE_HD uint64_t mg_measure(const XeMapOp& o, uint32_t at) {
   if (!o.g_mwidth || mg_src_zero(o, at)) return 0;
   return ms_field(o.vals + uint64_t(at) * o.value_size + o.g_moff, o.g_mwidth);
 }
-// LOCATE: the destination record of source slot sbase + s's group, or one claimed for it: mo_update_locate_item's
-// walk over the destination with the claim naming the source slot. True: this slot claimed a free or a
-// tombstone record (the caller counts them). An ARRAY destination only has its index checked.
+// LOCATE: the destination record of source slot sbase + s's group, or one claimed for it: mo_claim_walk over the
+// destination with the claim naming the source slot. True: this slot claimed a free or a tombstone record (the
+// caller counts them). An ARRAY destination only has its index checked.
 XE_HD bool mg_locate_item(const XeMapOp& o, uint32_t s) {
   const uint32_t at = o.sbase + s;
   uint64_t kw[XE_MAX_KEY / 8];
   mg_group_key(o, at, kw);
-  if (o.g_kind == XE_DM_ARRAY) {
-    if (kw[0] >= o.g_max_entries) mo_or32(o.ctr + kMoErr, kMoErrRange);
+  if (o.dst.kind == XE_DM_ARRAY) {
+    if (kw[0] >= o.dst.max_entries) mo_or32(o.ctr + kMoErr, kMoErrRange);
     return false;
   }
-  const XeMapOp d = mg_dst(o);
-  const uint64_t own = XE_SLOT_BUSY | ((uint64_t(at) + 1) << 32);
-  const uint32_t mask = d.cap - 1;
-  uint32_t idx = uint32_t(xe_hash_words(kw, d.kwords, d.key_size)) & mask;
-  for (uint32_t probe = 0; probe < d.cap;) {
-    uint64_t* r = d.recs + uint64_t(idx) * d.rwords;
-    const uint64_t w0 = mo_load64(r);
-    const uint32_t st = uint32_t(w0);
-    if (st & XE_SLOT_FULL) {
-      if (mo_key_eq(d, r, kw)) {
-        if (!(st & XE_SLOT_VLEN0) || (st & XE_SLOT_BUSY)) return false;
-        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) return false;  // nil-backed: claimed to be zeroed, not counted
-        continue;  // lost it (to another slot of this group): look again
-      }
-    } else if (st & XE_SLOT_TOMB) {  // holds key words
-      if (mo_key_eq(d, r, kw)) {
-        if (st & XE_SLOT_BUSY) return false;
-        if (mo_cas64(r, w0, uint64_t(st) | own) == w0) return true;
-        continue;
-      }
-    } else if (st & XE_SLOT_BUSY) {  // claimed in this launch by the source slot it names
-      uint64_t kj[XE_MAX_KEY / 8];
-      const uint32_t j = uint32_t(w0 >> 32) - 1;
-      bool eq = j >= o.sbase && j - o.sbase < o.nslots;
-      if (eq) {
-        mg_group_key(o, j, kj);
-        for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++) eq = eq && kj[k] == kw[k];
-      }
-      if (eq) return false;
-    } else {  // free
-      if (mo_cas64(r, w0, own) == w0) return true;
-      continue;
-    }
-    idx = (idx + 1) & mask;
-    probe++;
-  }
-  mo_or32(o.ctr + kMoErr, kMoErrFull);
-  return false;
+  const uint32_t c = mo_claim_walk<false, true>(o.dst, kw, XE_SLOT_BUSY | ((uint64_t(at) + 1) << 32), [&](uint32_t j) {
+    uint64_t kj[XE_MAX_KEY / 8];
+    if (j < o.sbase || j - o.sbase >= o.nslots) return false;
+    mg_group_key(o, j, kj);
+    return mo_words_eq(kj, kw);
+  });
+  if (c == kMoAbsent) mo_or32(o.ctr + kMoErr, kMoErrFull);
+  return (c & kMoFresh) != 0;
 }
 // UNDO, destination slot ds: a claimed record is what it was (the high half of word 0 was zero).
 XE_HD void mg_undo_item(const XeMapOp& o, uint32_t ds) {
-  uint64_t* r = o.g_recs + uint64_t(ds) * o.g_rwords;
+  uint64_t* r = o.dst.recs + uint64_t(ds) * o.dst.rwords;
   const uint32_t st = uint32_t(r[0]);
   if (st & XE_SLOT_BUSY) r[0] = uint64_t(st & ~XE_SLOT_BUSY);
 }
 // PUBLISH, destination slot ds, lane `sub` of the `lanes` that share it: nothing unless the record is claimed.
-XE_HD bool mg_claimed(const XeMapOp& o, uint32_t ds) { return (uint32_t(o.g_recs[uint64_t(ds) * o.g_rwords]) & XE_SLOT_BUSY) != 0; }
+XE_HD bool mg_claimed(const XeMapOp& o, uint32_t ds) { return (uint32_t(o.dst.recs[uint64_t(ds) * o.dst.rwords]) & XE_SLOT_BUSY) != 0; }
 XE_HD void mg_publish_item(const XeMapOp& o, uint32_t ds, uint32_t sub, uint32_t lanes) {
-  uint64_t* r = o.g_recs + uint64_t(ds) * o.g_rwords;
+  uint64_t* r = o.dst.recs + uint64_t(ds) * o.dst.rwords;
   const uint64_t w0 = r[0];
   const uint32_t st = uint32_t(w0);
   // the value: zero in the map and in the delta base (a tombstone's usually is, a nil-backed record's is not)
-  mo_move(o.g_vals + uint64_t(ds) * o.g_value_size, nullptr, o.g_value_size, sub, lanes);
-  mo_move(o.g_snap + uint64_t(ds) * o.g_value_size, nullptr, o.g_value_size, sub, lanes);
+  mo_move(o.dst.vals + uint64_t(ds) * o.dst.value_size, nullptr, o.dst.value_size, sub, lanes);
+  mo_move(o.dst.snap + uint64_t(ds) * o.dst.value_size, nullptr, o.dst.value_size, sub, lanes);
   if (sub != 0) return;
   if (!(st & (XE_SLOT_FULL | XE_SLOT_TOMB))) {  // claimed free: the key words are the claiming slot's group key
     uint64_t kw[XE_MAX_KEY / 8];
     mg_group_key(o, uint32_t(w0 >> 32) - 1, kw);
     for (uint32_t k = 0; k < XE_MAX_KEY / 8; k++)
-      if (k < o.g_kwords) r[1 + k] = kw[k];
+      if (k < o.dst.kwords) r[1 + k] = kw[k];
   }
   r[0] = XE_SLOT_FULL;
 }
-XE_HD void mg_publish_count(const XeMapOp& o) { *o.g_count += o.ctr[kMoNew]; }
-// ADD: the destination slot of source slot sbase + s's group, read-only (the kernel has a faster probe for
-// short records); kMoAbsent cannot happen after LOCATE and PUBLISH and is skipped.
-XE_HD uint32_t mg_slot_of(const XeMapOp& o, uint32_t s) {
+XE_HD void mg_publish_count(const XeMapOp& o) { *o.dst.count += o.ctr[kMoNew]; }
+// ADD: the destination slot of source slot sbase + s's group, read-only (find: as mo_slot_of's); kMoAbsent
+// cannot happen after LOCATE and PUBLISH and is skipped.
+template <class Find>
+XE_HD uint32_t mg_slot_of(const XeMapOp& o, uint32_t s, Find find) {
   uint64_t kw[XE_MAX_KEY / 8];
   mg_group_key(o, o.sbase + s, kw);
-  if (o.g_kind == XE_DM_ARRAY) return kw[0] < o.g_max_entries ? uint32_t(kw[0]) : kMoAbsent;
-  return mo_find(mg_dst(o), kw);
+  if (o.dst.kind == XE_DM_ARRAY) return kw[0] < o.dst.max_entries ? uint32_t(kw[0]) : kMoAbsent;
+  return find(o.dst, kw);
 }
 // ... and `count` entries with measures summing to `sum` added to destination slot ds, in the map and in the
 // delta base alike (so xe_map_delta sees no packet adds).
 XE_HD void mg_add_item(const XeMapOp& o, uint32_t ds, uint64_t count, uint64_t sum) {
-  uint8_t* v = o.g_vals + uint64_t(ds) * o.g_value_size;
-  uint8_t* b = o.g_snap + uint64_t(ds) * o.g_value_size;
+  uint8_t* v = o.dst.vals + uint64_t(ds) * o.dst.value_size;
+  uint8_t* b = o.dst.snap + uint64_t(ds) * o.dst.value_size;
   if (o.g_count_off != kMgNone) {
     mo_add64(reinterpret_cast<uint64_t*>(v + o.g_count_off), count);
     mo_add64(reinterpret_cast<uint64_t*>(b + o.g_count_off), count);
@@ -771,10 +742,10 @@ XE_HD void mg_add_item(const XeMapOp& o, uint32_t ds, uint64_t count, uint64_t s
 }
 
 // ---------------------------------------------------------------- compact
-// MARK, slot s (< cap): 0 free, 1 a tombstone, 2 an entry.
+// MARK, slot s (< cap): 1 free, 2 a tombstone, 0 an entry (the classes of the two bitmaps, as mt_cut_item's).
 XE_HD uint32_t mc_mark_item(const XeMapOp& o, uint32_t s) {
   const uint32_t st = uint32_t(o.recs[uint64_t(s) * o.rwords]);
-  return (st & XE_SLOT_FULL) ? 2u : (st & XE_SLOT_TOMB) ? 1u : 0u;
+  return (st & XE_SLOT_FULL) ? 0u : (st & XE_SLOT_TOMB) ? 2u : 1u;
 }
 // One bit of a bitmap: slot s sits in word s / 64 (tile s / kMsTile, round s / 64 % kMsRounds).
 XE_HD bool mc_bit(const uint64_t* bm, uint32_t s) { return (bm[s >> 6] >> (s & 63)) & 1; }
@@ -854,24 +825,44 @@ XE_HD bool mc_run_counts(const XeMapOp& o, uint32_t len, uint32_t first) {
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
-// The host simulation: the same items, one after another.
+// The host simulation: the same items, one after another. A pass that ballots: for every tile, round and lane
+// cls(t, r, lane) gives the slot's class; done(t, w1, w2, c1, c2) gets the tile's words of class 1 and class 2,
+// one per round, and their counts.
+template <class Cls, class Done>
+static inline void sim_tile_words(uint32_t tiles, Cls cls, Done done) {
+  for (uint32_t t = 0; t < tiles; t++) {
+    uint64_t w1[kMsRounds] = {}, w2[kMsRounds] = {};
+    uint32_t c1 = 0, c2 = 0;
+    for (uint32_t r = 0; r < kMsRounds; r++)
+      for (uint32_t lane = 0; lane < 64; lane++) {
+        const uint32_t c = cls(t, r, lane);
+        if (c == 1) w1[r] |= uint64_t(1) << lane, c1++;
+        if (c == 2) w2[r] |= uint64_t(1) << lane, c2++;
+      }
+    done(t, w1, w2, c1, c2);
+  }
+}
 static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
   const XeMapOp& o = *op;
   const uint32_t tiles = xe_ms_tiles(o.nslots);
-  if (step == XE_MO_SCAN_SELECT) {
-    for (uint32_t t = 0; t < tiles; t++) {
-      uint32_t cnt = 0;
-      for (uint32_t r = 0; r < kMsRounds; r++) {
-        uint64_t word = 0;
-        for (uint32_t lane = 0; lane < 64; lane++) {
-          const uint32_t s = t * kMsTile + r * 64 + lane;
-          if (s < o.nslots && ms_select_item(o, s)) word |= uint64_t(1) << lane;
-        }
-        o.bitmap[uint64_t(t) * kMsRounds + r] = word;
-        cnt += uint32_t(__builtin_popcountll(word));
-      }
-      o.tile[t] = cnt;
+  // a class per slot of the source (slots past nslots: none), and the two bitmaps and tile counts from the words
+  const auto slots = [&](auto item) {
+    return [&o, item](uint32_t t, uint32_t r, uint32_t lane) {
+      const uint32_t s = t * kMsTile + r * 64 + lane;
+      return s < o.nslots ? uint32_t(item(s)) : 0u;
+    };
+  };
+  const auto put = [&](uint32_t t, const uint64_t* w1, const uint64_t* w2, uint32_t count) {  // (w2 null: one bitmap)
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      o.bitmap[uint64_t(t) * kMsRounds + r] = w1[r];
+      if (w2) o.bitmap2[uint64_t(t) * kMsRounds + r] = w2[r];
     }
+    o.tile[t] = count;
+  };
+  using Words = const uint64_t*;
+  if (step == XE_MO_SCAN_SELECT) {
+    sim_tile_words(tiles, slots([&](uint32_t s) { return ms_select_item(o, s); }),
+                   [&](uint32_t t, Words w1, Words, uint32_t c1, uint32_t) { put(t, w1, nullptr, c1); });
     return 0;
   }
   if (step == XE_MO_SCAN_SCAN) {
@@ -923,41 +914,21 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
   if (step == XE_MO_TOP_CUT) {
     const uint64_t cut = mt_prefix(o);
     const uint32_t need = o.ctr[kMtNeed];
-    for (uint32_t t = 0; t < tiles; t++) {
-      uint32_t c1 = 0, c2 = 0;
-      for (uint32_t r = 0; r < kMsRounds; r++) {
-        uint64_t w1 = 0, w2 = 0;
-        for (uint32_t lane = 0; lane < 64; lane++) {
-          const uint32_t s = t * kMsTile + r * 64 + lane;
-          const uint32_t c = s < o.nslots ? mt_cut_item(o, s, cut, need) : 0;
-          if (c == 1) w1 |= uint64_t(1) << lane;
-          if (c == 2) w2 |= uint64_t(1) << lane;
-        }
-        o.bitmap[uint64_t(t) * kMsRounds + r] = w1;
-        o.bitmap2[uint64_t(t) * kMsRounds + r] = w2;
-        c1 += uint32_t(__builtin_popcountll(w1));
-        c2 += uint32_t(__builtin_popcountll(w2));
-      }
-      o.tile[t] = c1;
-      o.tile2[t] = c2;
-    }
+    sim_tile_words(tiles, slots([&](uint32_t s) { return mt_cut_item(o, s, cut, need); }),
+                   [&](uint32_t t, Words w1, Words w2, uint32_t c1, uint32_t c2) { put(t, w1, w2, c1), o.tile2[t] = c2; });
     return 0;
   }
-  if (step == XE_MO_TOP_TRIM) {
+  if (step == XE_MO_TOP_TRIM) {  // the equals kept join the first bitmap and its tile's count
     const uint32_t need = o.ctr[kMtNeed];
-    for (uint32_t t = 0; t < tiles; t++) {
-      uint32_t before = o.tile2[t], cnt = 0;
-      for (uint32_t r = 0; r < kMsRounds; r++) {
-        const uint64_t word = o.bitmap2[uint64_t(t) * kMsRounds + r];
-        uint64_t kept = 0;
-        for (uint32_t lane = 0; lane < 64; lane++)
-          if (mt_trim_item(lane, word, before, need)) kept |= uint64_t(1) << lane;
-        o.bitmap[uint64_t(t) * kMsRounds + r] |= kept;
-        cnt += uint32_t(__builtin_popcountll(kept));
-        before += uint32_t(__builtin_popcountll(word));
-      }
-      o.tile[t] += cnt;
-    }
+    const auto kept = [&](uint32_t t, uint32_t r, uint32_t lane) {
+      uint32_t before = o.tile2[t];
+      for (uint32_t q = 0; q < r; q++) before += uint32_t(__builtin_popcountll(o.bitmap2[uint64_t(t) * kMsRounds + q]));
+      return uint32_t(mt_trim_item(lane, o.bitmap2[uint64_t(t) * kMsRounds + r], before, need));
+    };
+    sim_tile_words(tiles, kept, [&](uint32_t t, Words w1, Words, uint32_t c1, uint32_t) {
+      for (uint32_t r = 0; r < kMsRounds; r++) o.bitmap[uint64_t(t) * kMsRounds + r] |= w1[r];
+      o.tile[t] += c1;
+    });
     return 0;
   }
   if (step == XE_MO_TOP_STATS) {
@@ -976,7 +947,7 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
           if (step == XE_MO_GROUP_LOCATE) {
             if (mg_locate_item(o, s)) o.ctr[kMoNew]++;
           } else {
-            const uint32_t ds = mg_slot_of(o, s);
+            const uint32_t ds = mg_slot_of(o, s, mo_find);
             if (ds != kMoAbsent) mg_add_item(o, ds, 1, mg_measure(o, o.sbase + s));
           }
         }
@@ -984,32 +955,17 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
     return 0;
   }
   if (step == XE_MO_GROUP_UNDO || step == XE_MO_GROUP_PUBLISH) {  // over the destination table
-    if (o.g_kind != XE_DM_HASH) return 0;
-    for (uint32_t ds = 0; ds < o.g_cap; ds++) {
+    if (o.dst.kind != XE_DM_HASH) return 0;
+    for (uint32_t ds = 0; ds < o.dst.cap; ds++) {
       if (step == XE_MO_GROUP_UNDO) mg_undo_item(o, ds);
       else if (mg_claimed(o, ds)) mg_publish_item(o, ds, 0, 1);
     }
     if (step == XE_MO_GROUP_PUBLISH) mg_publish_count(o);
     return 0;
   }
-  if (step == XE_MO_COMPACT_MARK) {
-    for (uint32_t t = 0; t < tiles; t++) {
-      uint32_t tombs = 0;
-      for (uint32_t r = 0; r < kMsRounds; r++) {
-        uint64_t fr = 0, tb = 0;
-        for (uint32_t lane = 0; lane < 64; lane++) {
-          const uint32_t s = t * kMsTile + r * 64 + lane;
-          const uint32_t c = s < o.nslots ? mc_mark_item(o, s) : 2;
-          if (c == 0) fr |= uint64_t(1) << lane;
-          if (c == 1) tb |= uint64_t(1) << lane;
-        }
-        o.bitmap[uint64_t(t) * kMsRounds + r] = fr;
-        o.bitmap2[uint64_t(t) * kMsRounds + r] = tb;
-        tombs += uint32_t(__builtin_popcountll(tb));
-        o.ctr[kMcFree] += uint32_t(__builtin_popcountll(fr));
-      }
-      o.tile[t] = tombs;
-    }
+  if (step == XE_MO_COMPACT_MARK) {  // the tile counts are the tombstones, the free records go to the counters
+    sim_tile_words(tiles, slots([&](uint32_t s) { return mc_mark_item(o, s); }),
+                   [&](uint32_t t, Words w1, Words w2, uint32_t c1, uint32_t c2) { put(t, w1, w2, c2), o.ctr[kMcFree] += c1; });
     return 0;
   }
   if (step == XE_MO_COMPACT_REBUILD) {
@@ -1028,13 +984,13 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
   }
   for (uint32_t i = 0; i < o.n; i++) {
     switch (step) {
-      case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i), true); break;
+      case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i, mo_find), true); break;
       case XE_MO_LOOKUP_VALUE: mo_lookup_value_item(o, i, 0, 1); break;
       case XE_MO_UPDATE_LOCATE: if (mo_update_locate_item(o, i)) o.ctr[kMoNew]++; break;
       case XE_MO_UPDATE_UNDO: mo_update_undo_item(o, i); break;
       case XE_MO_UPDATE_MARK: mo_update_mark_item(o, i); break;
       case XE_MO_UPDATE_COPY: mo_update_copy_item(o, i, 0, 1); break;
-      case XE_MO_DELETE_FIND: mo_find_finish(o, i, mo_slot_of(o, i), false); break;
+      case XE_MO_DELETE_FIND: mo_find_finish(o, i, mo_slot_of(o, i, mo_find), false); break;
       case XE_MO_DELETE_CLAIM: mo_delete_claim_item(o, i); break;
       case XE_MO_DELETE_ZERO: mo_delete_zero_item(o, i, 0, 1); break;
       case XE_MO_SCAN_COPY: ms_copy_item(o, i, 0, 1); break;

@@ -23,7 +23,7 @@ constexpr uint32_t kMoThreads = 256, kMoOneTurn = 256, kMoMaxBlocks = 2048;
 // nor a tombstone. A chain that stays inside the line costs one round trip. (cap is a multiple of the
 // group: it is a power of two >= 16.)
 template <uint32_t RW>
-__device__ __forceinline__ uint32_t find_grouped(const XeMapOp& o, const uint64_t* kw) {
+__device__ __forceinline__ uint32_t find_grouped(const XeMapView& o, const uint64_t* kw) {
   constexpr uint32_t G = 8 / RW, KW = RW - 1;
   const uint32_t mask = o.cap - 1;
   uint32_t idx = uint32_t(xe_hash_words(kw, o.kwords, o.key_size)) & mask;
@@ -63,13 +63,17 @@ __device__ __forceinline__ uint32_t find_grouped(const XeMapOp& o, const uint64_
   return kMoAbsent;
 }
 
-__device__ __forceinline__ uint32_t find_slot(const XeMapOp& o, uint32_t i) {
-  if (o.kind == XE_DM_ARRAY || o.key_size == 0) return mo_slot_of(o, i);
-  uint64_t kw[XE_MAX_KEY / 8];
-  mo_load_key(o, i, kw);
-  if (o.rwords == 2) return find_grouped<2>(o, kw);
-  if (o.rwords == 4) return find_grouped<4>(o, kw);
-  return mo_find(o, kw);
+// The kernels' read-only probe of HASH table v (the Find of mo_slot_of and mg_slot_of); the empty key's rwords is 1.
+__device__ __forceinline__ uint32_t find_slot(const XeMapView& v, const uint64_t* kw) {
+  if (v.rwords == 2) return find_grouped<2>(v, kw);
+  if (v.rwords == 4) return find_grouped<4>(v, kw);
+  return mo_find(v, kw);
+}
+
+// `mine` counted into *ctr once per wave (every lane of the wave is here).
+__device__ __forceinline__ void count_once_per_wave(uint32_t* ctr, bool mine) {
+  const unsigned long long b = __ballot(mine);
+  if (b && (threadIdx.x & 63) == uint32_t(__builtin_ctzll(b))) mo_add32(ctr, uint32_t(__popcll(b)));
 }
 
 // one entry per lane
@@ -83,8 +87,8 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_lane_kernel(XeMapOp o, ui
     bool fresh = false;
     if (in) {
       switch (step) {
-        case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, find_slot(o, i), true); break;
-        case XE_MO_DELETE_FIND: mo_find_finish(o, i, find_slot(o, i), false); break;
+        case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i, find_slot), true); break;
+        case XE_MO_DELETE_FIND: mo_find_finish(o, i, mo_slot_of(o, i, find_slot), false); break;
         case XE_MO_UPDATE_LOCATE: fresh = mo_update_locate_item(o, i); break;
         case XE_MO_UPDATE_UNDO: mo_update_undo_item(o, i); break;
         case XE_MO_UPDATE_MARK: mo_update_mark_item(o, i); break;
@@ -92,10 +96,7 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_lane_kernel(XeMapOp o, ui
         default: break;
       }
     }
-    if (step == XE_MO_UPDATE_LOCATE) {  // the claims, counted once per wave
-      const unsigned long long b = __ballot(fresh);
-      if (b && (threadIdx.x & 63) == uint32_t(__builtin_ctzll(b))) mo_add32(o.ctr + kMoNew, uint32_t(__popcll(b)));
-    }
+    if (step == XE_MO_UPDATE_LOCATE) count_once_per_wave(o.ctr + kMoNew, fresh);  // the claims
   }
 }
 
@@ -120,13 +121,23 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_value_kernel(XeMapOp o, u
 // of one slot per lane; the waves stride over the tiles. A wave's round reads word 0 of 64 consecutive
 // records (512 to 4,096 contiguous bytes) and, for the FULL ones, the field's bytes of 64 consecutive
 // values; the rounds are independent, so their loads are in flight together.
-__global__ void __launch_bounds__(kMoThreads) xe_mapscan_select_kernel(XeMapOp o, uint32_t tiles) {
+template <class F>
+__device__ __forceinline__ void tile_walk(uint32_t tiles, F f) {  // f(t, lane)
   const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) f(t, lane);
+}
+__device__ __forceinline__ uint32_t tile_slot(uint32_t t, uint32_t r, uint32_t lane) { return t * kMsTile + r * 64 + lane; }
+__device__ __forceinline__ void tile_words(const uint64_t* bitmap, uint32_t t, uint64_t (&word)[kMsRounds]) {
+#pragma unroll
+  for (uint32_t r = 0; r < kMsRounds; r++) word[r] = bitmap[uint64_t(t) * kMsRounds + r];
+}
+
+__global__ void __launch_bounds__(kMoThreads) xe_mapscan_select_kernel(XeMapOp o, uint32_t tiles) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     bool hit[kMsRounds];
 #pragma unroll
     for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t s = t * kMsTile + r * 64 + lane;
+      const uint32_t s = tile_slot(t, r, lane);
       hit[r] = s < o.nslots && ms_select_item(o, s);
     }
     uint32_t cnt = 0;
@@ -137,38 +148,43 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapscan_select_kernel(XeMapOp o
       cnt += uint32_t(__popcll(b));
     }
     if (lane == 0) o.tile[t] = cnt;
-  }
+  });
 }
 
-// Exclusive sums of the tile counts in place, by one workgroup: four counts per lane, an inclusive scan
-// across each wave, the waves' sums through LDS, a carry from pass to pass.
+// The exclusive sum of x over the workgroup's kThreads threads, and the sum of all: an inclusive scan across
+// each wave, the waves' sums through LDS (wsum: a word per wave; a barrier before it is written again).
+template <uint32_t kThreads>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t* wsum, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t inc = x;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += y;
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  uint32_t before = inc - x, all = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kThreads / 64; k++) {
+    const uint32_t s = wsum[k];
+    before += k < w ? s : 0;
+    all += s;
+  }
+  *total = all;
+  return before;
+}
+
+// Exclusive sums of the tile counts in place, by one workgroup: four counts per lane, a carry from pass to pass.
 __global__ void __launch_bounds__(kMsScanThreads) xe_mapscan_scan_kernel(XeMapOp o, uint32_t tiles) {
-  constexpr uint32_t kWaves = kMsScanThreads / 64;
-  __shared__ uint32_t wsum[kWaves];
-  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  __shared__ uint32_t wsum[kMsScanThreads / 64];
   uint32_t carry = 0;
   for (uint32_t base = 0; base < tiles; base += kMsScanPass) {
-    const uint32_t at = base + t * 4;
-    uint32_t x[4];
+    const uint32_t at = base + threadIdx.x * 4;
+    uint32_t x[4], all;
 #pragma unroll
     for (uint32_t j = 0; j < 4; j++) x[j] = at + j < tiles ? o.tile[at + j] : 0;
-    uint32_t inc = x[0] + x[1] + x[2] + x[3];
-    const uint32_t sum = inc;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += y;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t before = carry, all = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kWaves; k++) {
-      const uint32_t s = wsum[k];
-      before += k < w ? s : 0;
-      all += s;
-    }
-    uint32_t e = before + inc - sum;
+    uint32_t e = carry + block_exclusive_scan<kMsScanThreads>(x[0] + x[1] + x[2] + x[3], wsum, &all);
 #pragma unroll
     for (uint32_t j = 0; j < 4; j++) {
       if (at + j < tiles) o.tile[at + j] = e;
@@ -177,23 +193,21 @@ __global__ void __launch_bounds__(kMsScanThreads) xe_mapscan_scan_kernel(XeMapOp
     carry += all;
     __syncthreads();  // (wsum is written again in the next pass)
   }
-  if (t == 0) o.ctr[kMoMatched] = carry;
+  if (threadIdx.x == 0) o.ctr[kMoMatched] = carry;
 }
 
 __global__ void __launch_bounds__(kMoThreads) xe_mapscan_scatter_kernel(XeMapOp o, uint32_t tiles) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     uint32_t before = o.tile[t];
-    if (before >= o.n) continue;  // every entry to report lies in front of this tile
+    if (before >= o.n) return;  // every entry to report lies in front of this tile
     uint64_t word[kMsRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap[uint64_t(t) * kMsRounds + r];
+    tile_words(o.bitmap, t, word);
 #pragma unroll
     for (uint32_t r = 0; r < kMsRounds; r++) {
       ms_scatter_item(o, t, r, lane, word[r], before);
       before += uint32_t(__popcll(word[r]));
     }
-  }
+  });
 }
 
 // ---- top / evict / stats. PREFIX, CUT, TRIM and STATS keep SELECT's shape (a wave per tile, four
@@ -208,13 +222,12 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_prefix_kernel(XeMapOp o,
   hist[threadIdx.x] = 0;
   __syncthreads();
   const uint64_t prefix = mt_prefix(o);
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     uint64_t key[kMsRounds];
     bool in[kMsRounds];
 #pragma unroll
     for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t s = t * kMsTile + r * 64 + lane;
+      const uint32_t s = tile_slot(t, r, lane);
       key[r] = 0;
       in[r] = s < o.nslots && mt_key_item(o, s, &key[r]) && mt_in_prefix(o, key[r], prefix);
     }
@@ -228,34 +241,19 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_prefix_kernel(XeMapOp o,
       if (lane == lead) atomicAdd(&hist[lbin], uint32_t(__popcll(same)));
       else if (in[r] && bin != lbin) atomicAdd(&hist[bin], 1u);
     }
-  }
+  });
   __syncthreads();
   const uint32_t c = hist[threadIdx.x];
   if (c) mo_add32(o.bins + threadIdx.x, c);
 }
 
-// PICK: one bin per thread; the exclusive sums of the bins as in xe_mapscan_scan_kernel.
-__global__ void __launch_bounds__(kMtBins) xe_maptop_pick_kernel(XeMapOp o) {
-  constexpr uint32_t kWaves = kMtBins / 64;
-  __shared__ uint32_t wsum[kWaves];
-  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const uint32_t c = o.bins[t];
-  uint32_t need = o.ctr[kMtNeed];
-  uint32_t inc = c;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += y;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();  // (also: every thread has read the counters before one of them writes)
-  uint32_t before = inc - c, total = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < kWaves; k++) {
-    const uint32_t s = wsum[k];
-    before += k < w ? s : 0;
-    total += s;
-  }
+// PICK: one bin per thread and the exclusive sums of the bins.
+__global__ void __launch_bounds__(kMtBins) xe_maptop_pick_kernel(XeMapOp o, uint32_t) {
+  __shared__ uint32_t wsum[kMtBins / 64];
+  const uint32_t t = threadIdx.x, c = o.bins[t];
+  uint32_t need = o.ctr[kMtNeed], total;
+  // (the scan's barrier also: every thread has read the counters before one of them writes)
+  const uint32_t before = block_exclusive_scan<kMtBins>(c, wsum, &total);
   if (o.t_pass == 0) {
     need = total < o.t_k ? total : o.t_k;
     if (t == 0) o.ctr[kMtMatched] = total;
@@ -264,16 +262,17 @@ __global__ void __launch_bounds__(kMtBins) xe_maptop_pick_kernel(XeMapOp o) {
   o.bins[t] = 0;
 }
 
-__global__ void __launch_bounds__(kMoThreads) xe_maptop_cut_kernel(XeMapOp o, uint32_t tiles) {
-  const uint64_t cut = mt_prefix(o);
-  const uint32_t need = o.ctr[kMtNeed];
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+// CUT and MARK: one pass over the source's slots that sorts them into two classes. cls(s) of a slot below
+// nslots: 1, 2 or neither; one ballot a round into the first bitmap with the bit "class 1", one into the second
+// with the bit "class 2"; lane 0 then gets the tile's two counts: done(t, c1, c2).
+template <class Cls, class Done>
+__device__ __forceinline__ void two_class_pass(const XeMapOp& o, uint32_t tiles, Cls cls, Done done) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     uint32_t c[kMsRounds];
 #pragma unroll
     for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t s = t * kMsTile + r * 64 + lane;
-      c[r] = s < o.nslots ? mt_cut_item(o, s, cut, need) : 0;
+      const uint32_t s = tile_slot(t, r, lane);
+      c[r] = s < o.nslots ? cls(s) : 0;
     }
     uint32_t c1 = 0, c2 = 0;
 #pragma unroll
@@ -286,22 +285,26 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_cut_kernel(XeMapOp o, ui
       c1 += uint32_t(__popcll(b1));
       c2 += uint32_t(__popcll(b2));
     }
-    if (lane == 0) {
-      o.tile[t] = c1;
-      o.tile2[t] = c2;
-    }
-  }
+    if (lane == 0) done(t, c1, c2);
+  });
+}
+
+__global__ void __launch_bounds__(kMoThreads) xe_maptop_cut_kernel(XeMapOp o, uint32_t tiles) {
+  const uint64_t cut = mt_prefix(o);
+  const uint32_t need = o.ctr[kMtNeed];
+  two_class_pass(o, tiles, [&](uint32_t s) { return mt_cut_item(o, s, cut, need); }, [&](uint32_t t, uint32_t c1, uint32_t c2) {
+    o.tile[t] = c1;
+    o.tile2[t] = c2;
+  });
 }
 
 __global__ void __launch_bounds__(kMoThreads) xe_maptop_trim_kernel(XeMapOp o, uint32_t tiles) {
   const uint32_t need = o.ctr[kMtNeed];
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     uint32_t before = o.tile2[t];
-    if (before >= need) continue;  // every equal to keep lies in front of this tile
+    if (before >= need) return;  // every equal to keep lies in front of this tile
     uint64_t word[kMsRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap2[uint64_t(t) * kMsRounds + r];
+    tile_words(o.bitmap2, t, word);
     uint32_t cnt = 0;
 #pragma unroll
     for (uint32_t r = 0; r < kMsRounds; r++) {
@@ -311,19 +314,18 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_trim_kernel(XeMapOp o, u
       before += uint32_t(__popcll(word[r]));
     }
     if (lane == 0 && cnt) o.tile[t] += cnt;
-  }
+  });
 }
 
 __global__ void __launch_bounds__(kMoThreads) xe_maptop_stats_kernel(XeMapOp o, uint32_t tiles) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
   XeMtStats a{};
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
 #pragma unroll
     for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t s = t * kMsTile + r * 64 + lane;
+      const uint32_t s = tile_slot(t, r, lane);
       if (s < o.nslots) mt_stats_item(o, s, &a);
     }
-  }
+  });
 #pragma unroll
   for (uint32_t d = 32; d; d >>= 1) {
     const uint64_t cn = __shfl_xor((unsigned long long)a.count, int(d), 64), sm = __shfl_xor((unsigned long long)a.sum, int(d), 64);
@@ -335,7 +337,7 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_stats_kernel(XeMapOp o, 
   }
   // the waves of a workgroup meet in LDS: the atomics all go to the same four words, so fewer is faster
   __shared__ XeMtStats part[kMoThreads / 64];
-  if (lane == 0) part[threadIdx.x >> 6] = a;
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
@@ -353,30 +355,15 @@ __global__ void __launch_bounds__(kMoThreads) xe_maptop_stats_kernel(XeMapOp o, 
 // destination table a wave per tile (SELECT's shape). A lane's work is a probe of the destination, so the
 // rounds of a tile run one after another.
 __global__ void __launch_bounds__(kMoThreads) xe_mapgroup_locate_kernel(XeMapOp o, uint32_t tiles) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     uint64_t word[kMsRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap[uint64_t(t) * kMsRounds + r];
+    tile_words(o.bitmap, t, word);
 #pragma unroll 1
     for (uint32_t r = 0; r < kMsRounds; r++) {
       if (!word[r]) continue;
-      const bool fresh = ((word[r] >> lane) & 1) && mg_locate_item(o, t * kMsTile + r * 64 + lane);
-      const unsigned long long b = __ballot(fresh);  // the claims, counted once per wave
-      if (b && lane == uint32_t(__builtin_ctzll(b))) mo_add32(o.ctr + kMoNew, uint32_t(__popcll(b)));
+      count_once_per_wave(o.ctr + kMoNew, ((word[r] >> lane) & 1) && mg_locate_item(o, tile_slot(t, r, lane)));  // the claims
     }
-  }
-}
-
-// The read-only probe of ADD: find_slot's choice of walk, over the destination.
-__device__ __forceinline__ uint32_t group_slot(const XeMapOp& o, uint32_t s) {
-  if (o.g_kind == XE_DM_ARRAY) return mg_slot_of(o, s);
-  uint64_t kw[XE_MAX_KEY / 8];
-  mg_group_key(o, o.sbase + s, kw);
-  const XeMapOp d = mg_dst(o);
-  if (d.rwords == 2) return find_grouped<2>(d, kw);
-  if (d.rwords == 4) return find_grouped<4>(d, kw);
-  return mo_find(d, kw);
+  });
 }
 
 // ADD. A low-cardinality group-by sends most of a round's lanes to one or two destination slots, and many
@@ -385,20 +372,18 @@ __device__ __forceinline__ uint32_t group_slot(const XeMapOp& o, uint32_t s) {
 // popcount and their measures a wave sum, the leader adds once for all of them; kMgLeaders times a round, the
 // lanes still left add singly.
 __global__ void __launch_bounds__(kMoThreads) xe_mapgroup_add_kernel(XeMapOp o, uint32_t tiles) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
   const bool measured = o.g_sum_off != kMgNone;
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
     uint64_t word[kMsRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kMsRounds; r++) word[r] = o.bitmap[uint64_t(t) * kMsRounds + r];
+    tile_words(o.bitmap, t, word);
 #pragma unroll 1
     for (uint32_t r = 0; r < kMsRounds; r++) {
       if (!word[r]) continue;
-      const uint32_t s = t * kMsTile + r * 64 + lane;
+      const uint32_t s = tile_slot(t, r, lane);
       uint32_t ds = kMoAbsent;
       uint64_t m = 0;
       if ((word[r] >> lane) & 1) {
-        ds = group_slot(o, s);
+        ds = mg_slot_of(o, s, find_slot);
         if (measured) m = mg_measure(o, o.sbase + s);
       }
       bool left = ds != kMoAbsent;
@@ -419,25 +404,24 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapgroup_add_kernel(XeMapOp o, 
       }
       if (left) mg_add_item(o, ds, 1, m);
     }
-  }
+  });
 }
 
 // UNDO / PUBLISH over the destination table. PUBLISH: a value of up to kMoInline bytes is zeroed by its record's
 // lane; a larger one by the whole wave, one claimed record of the round after another.
-__global__ void __launch_bounds__(kMoThreads) xe_mapgroup_dst_kernel(XeMapOp o, uint32_t tiles, uint32_t step) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
+__global__ void __launch_bounds__(kMoThreads) xe_mapgroup_dst_kernel(XeMapOp o, uint32_t step) {
   if (step == XE_MO_GROUP_PUBLISH && blockIdx.x == 0 && threadIdx.x == 0) mg_publish_count(o);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(xe_ms_tiles(o.dst.cap), [&](uint32_t t, uint32_t lane) {
 #pragma unroll 1
     for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t ds = t * kMsTile + r * 64 + lane;
-      const bool in = ds < o.g_cap;
+      const uint32_t ds = tile_slot(t, r, lane);
+      const bool in = ds < o.dst.cap;
       if (step == XE_MO_GROUP_UNDO) {
         if (in) mg_undo_item(o, ds);
         continue;
       }
       const bool claimed = in && mg_claimed(o, ds);
-      if (o.g_value_size <= kMoInline) {
+      if (o.dst.value_size <= kMoInline) {
         if (claimed) mg_publish_item(o, ds, 0, 1);
         continue;
       }
@@ -445,50 +429,29 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapgroup_dst_kernel(XeMapOp o, 
       while (todo) {
         const uint32_t l = uint32_t(__builtin_ctzll(todo));
         todo &= todo - 1;
-        mg_publish_item(o, t * kMsTile + r * 64 + l, lane, 64);
+        mg_publish_item(o, tile_slot(t, r, l), lane, 64);
       }
     }
-  }
+  });
 }
 
 // ---- compact. MARK has SELECT's shape and reads word 0 of every record once: two ballots a round, the tile's
 // tombstones for SCAN, the tile's free records in one atomic.
 __global__ void __launch_bounds__(kMoThreads) xe_mapcompact_mark_kernel(XeMapOp o, uint32_t tiles) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
-    uint32_t c[kMsRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t s = t * kMsTile + r * 64 + lane;
-      c[r] = s < o.nslots ? mc_mark_item(o, s) : 2;
-    }
-    uint32_t tombs = 0, frees = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kMsRounds; r++) {
-      const unsigned long long fr = __ballot(c[r] == 0), tb = __ballot(c[r] == 1);
-      if (lane == 0) {
-        o.bitmap[uint64_t(t) * kMsRounds + r] = fr;
-        o.bitmap2[uint64_t(t) * kMsRounds + r] = tb;
-      }
-      frees += uint32_t(__popcll(fr));
-      tombs += uint32_t(__popcll(tb));
-    }
-    if (lane == 0) {
-      o.tile[t] = tombs;
-      if (frees) mo_add32(o.ctr + kMcFree, frees);
-    }
-  }
+  two_class_pass(o, tiles, [&](uint32_t s) { return mc_mark_item(o, s); }, [&](uint32_t t, uint32_t frees, uint32_t tombs) {
+    o.tile[t] = tombs;
+    if (frees) mo_add32(o.ctr + kMcFree, frees);
+  });
 }
 
 // REBUILD: a lane whose slot starts a run measures it from the bitmaps. Values of up to kMoInline bytes: the lane
 // walks its run alone. Larger values: the wave takes the runs of the round one after another, as PUBLISH takes
 // its records: lane 0 decides where each record goes, every lane moves its share of the value.
 __global__ void __launch_bounds__(kMoThreads) xe_mapcompact_rebuild_kernel(XeMapOp o, uint32_t tiles) {
-  const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kMoThreads / 64);
-  for (uint32_t t = blockIdx.x * (kMoThreads / 64) + (threadIdx.x >> 6); t < tiles; t += waves) {
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
 #pragma unroll 1
     for (uint32_t r = 0; r < kMsRounds; r++) {
-      const uint32_t s = t * kMsTile + r * 64 + lane;
+      const uint32_t s = tile_slot(t, r, lane);
       uint32_t len = 0, first = 0, moved = 0;
       bool mine = false;
       if (s < o.nslots && mc_run_start(o, s)) {
@@ -523,58 +486,77 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapcompact_rebuild_kernel(XeMap
       for (uint32_t d = 32; d; d >>= 1) moved += uint32_t(__shfl_xor(int(moved), int(d), 64));
       if (lane == 0 && moved) mo_add32(o.ctr + kMcMoved, moved);
     }
-  }
+  });
+}
+
+// The steps: how each is launched, and its kernel. kLane / kValue: one batch entry per lane / per sub-group of
+// xe_mo_lanes lanes (the kernel's second argument is the step; a value step's kernel is the instantiation for
+// those lanes). kTileSrc / kTileDst: a wave per tile of the source's slots (the second argument is their
+// number) / of the group's destination table, a HASH one (the step). kOneGroup: one workgroup, once the source
+// has a tile.
+enum MoShape : uint32_t { kNoShape = 0, kLane, kValue, kTileSrc, kTileDst, kOneGroup };
+using MoKernel = void (*)(XeMapOp, uint32_t);
+struct MoStep {
+  MoShape shape;
+  MoKernel kernel;
+};
+struct MoTable {
+  MoStep row[XE_MO_STEPS];
+};
+constexpr MoTable mo_table() {
+  MoTable t{};
+  for (uint32_t s : {XE_MO_LOOKUP_FIND, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM})
+    t.row[s] = {kLane, xe_mapop_lane_kernel};
+  for (uint32_t s : {XE_MO_LOOKUP_VALUE, XE_MO_UPDATE_COPY, XE_MO_DELETE_ZERO, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE}) t.row[s] = {kValue, nullptr};
+  t.row[XE_MO_SCAN_SELECT] = {kTileSrc, xe_mapscan_select_kernel};
+  t.row[XE_MO_SCAN_SCAN] = {kOneGroup, xe_mapscan_scan_kernel};
+  t.row[XE_MO_SCAN_SCATTER] = {kTileSrc, xe_mapscan_scatter_kernel};
+  t.row[XE_MO_TOP_PREFIX] = {kTileSrc, xe_maptop_prefix_kernel};
+  t.row[XE_MO_TOP_PICK] = {kOneGroup, xe_maptop_pick_kernel};
+  t.row[XE_MO_TOP_CUT] = {kTileSrc, xe_maptop_cut_kernel};
+  t.row[XE_MO_TOP_TRIM] = {kTileSrc, xe_maptop_trim_kernel};
+  t.row[XE_MO_TOP_STATS] = {kTileSrc, xe_maptop_stats_kernel};
+  t.row[XE_MO_GROUP_LOCATE] = {kTileSrc, xe_mapgroup_locate_kernel};
+  t.row[XE_MO_GROUP_UNDO] = t.row[XE_MO_GROUP_PUBLISH] = {kTileDst, xe_mapgroup_dst_kernel};
+  t.row[XE_MO_GROUP_ADD] = {kTileSrc, xe_mapgroup_add_kernel};
+  t.row[XE_MO_COMPACT_MARK] = {kTileSrc, xe_mapcompact_mark_kernel};
+  t.row[XE_MO_COMPACT_REBUILD] = {kTileSrc, xe_mapcompact_rebuild_kernel};
+  return t;
+}
+constexpr MoTable kMoSteps = mo_table();
+constexpr bool mo_steps_filled() {
+  for (const MoStep& r : kMoSteps.row)
+    if (r.shape == kNoShape || (r.kernel == nullptr) != (r.shape == kValue)) return false;
+  return true;
+}
+static_assert(sizeof kMoSteps.row / sizeof kMoSteps.row[0] == XE_MO_STEPS && mo_steps_filled(), "one filled row per step");
+static_assert(kMsScanThreads == kMoThreads && kMtBins == kMoThreads, "every step's workgroup has kMoThreads threads");
+
+// The grid of `want` workgroups' worth of work (the head of this file).
+uint32_t mo_blocks(uint64_t want) {
+  return uint32_t(want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks);
 }
 
 }  // namespace
 
-// SELECT / SCATTER and the tile passes of top / evict / stats / group: a wave per tile up to kMoOneTurn workgroups, then a quarter of the workgroups that
-// would take, between kMoOneTurn and kMoMaxBlocks (the file's policy), the waves striding over the tiles.
-static int launch_mapscan(const XeMapOp* op, uint32_t step, hipStream_t s) {
-  // UNDO and PUBLISH walk the destination table, every other step the source's slots
-  const bool dst = step == XE_MO_GROUP_UNDO || step == XE_MO_GROUP_PUBLISH;
-  if (dst && op->g_kind != XE_DM_HASH) return 0;
-  const uint32_t tiles = xe_ms_tiles(dst ? op->g_cap : op->nslots);
-  if (!tiles) return 0;
-  if (step == XE_MO_SCAN_SCAN) {
-    hipLaunchKernelGGL(xe_mapscan_scan_kernel, dim3(1), dim3(kMsScanThreads), 0, s, *op, tiles);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  if (step == XE_MO_TOP_PICK) {
-    hipLaunchKernelGGL(xe_maptop_pick_kernel, dim3(1), dim3(kMtBins), 0, s, *op);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  const uint32_t want = (tiles + kMoThreads / 64 - 1) / (kMoThreads / 64);
-  const uint32_t blocks = want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks;
-  if (step == XE_MO_SCAN_SELECT) hipLaunchKernelGGL(xe_mapscan_select_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_TOP_PREFIX) hipLaunchKernelGGL(xe_maptop_prefix_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_TOP_CUT) hipLaunchKernelGGL(xe_maptop_cut_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_TOP_TRIM) hipLaunchKernelGGL(xe_maptop_trim_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_TOP_STATS) hipLaunchKernelGGL(xe_maptop_stats_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_GROUP_LOCATE) hipLaunchKernelGGL(xe_mapgroup_locate_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_GROUP_ADD) hipLaunchKernelGGL(xe_mapgroup_add_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_COMPACT_MARK) hipLaunchKernelGGL(xe_mapcompact_mark_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (step == XE_MO_COMPACT_REBUILD) hipLaunchKernelGGL(xe_mapcompact_rebuild_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  else if (dst) hipLaunchKernelGGL(xe_mapgroup_dst_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles, step);
-  else hipLaunchKernelGGL(xe_mapscan_scatter_kernel, dim3(blocks), dim3(kMoThreads), 0, s, *op, tiles);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream) {
-  hipStream_t s = hipStream_t(stream);
-  if (step == XE_MO_SCAN_SELECT || step == XE_MO_SCAN_SCAN || step == XE_MO_SCAN_SCATTER || step >= XE_MO_TOP_PREFIX)
-    return launch_mapscan(op, step, s);
-  if (!op->n) return 0;
-  const bool value = step == XE_MO_LOOKUP_VALUE || step == XE_MO_UPDATE_COPY || step == XE_MO_DELETE_ZERO ||
-                     step == XE_MO_SCAN_COPY || step == XE_MO_SCAN_EXPIRE;
-  const uint32_t lanes = value ? xe_mo_lanes(op->value_size) : 1, per = kMoThreads / lanes;
-  const uint64_t want = (uint64_t(op->n) + per - 1) / per;
-  const uint64_t blocks = want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks;
-  const dim3 grid{uint32_t(blocks)}, block(kMoThreads);
-  if (!value) hipLaunchKernelGGL(xe_mapop_lane_kernel, grid, block, 0, s, *op, step);
-  else if (lanes == 1) hipLaunchKernelGGL(xe_mapop_value_kernel<1>, grid, block, 0, s, *op, step);
-  else if (lanes == 4) hipLaunchKernelGGL(xe_mapop_value_kernel<4>, grid, block, 0, s, *op, step);
-  else if (lanes == 16) hipLaunchKernelGGL(xe_mapop_value_kernel<16>, grid, block, 0, s, *op, step);
-  else hipLaunchKernelGGL(xe_mapop_value_kernel<64>, grid, block, 0, s, *op, step);
+  if (step >= XE_MO_STEPS) return -1;
+  const MoShape shape = kMoSteps.row[step].shape;
+  MoKernel kernel = kMoSteps.row[step].kernel;
+  uint32_t blocks = 1, arg = step;
+  if (shape == kLane || shape == kValue) {
+    if (!op->n) return 0;
+    const uint32_t lanes = shape == kValue ? xe_mo_lanes(op->value_size) : 1, per = kMoThreads / lanes;
+    blocks = mo_blocks((uint64_t(op->n) + per - 1) / per);
+    if (shape == kValue)
+      kernel = lanes == 1 ? xe_mapop_value_kernel<1> : lanes == 4 ? xe_mapop_value_kernel<4> : lanes == 16 ? xe_mapop_value_kernel<16> : xe_mapop_value_kernel<64>;
+  } else {
+    if (shape == kTileDst && op->dst.kind != XE_DM_HASH) return 0;
+    const uint32_t tiles = xe_ms_tiles(shape == kTileDst ? op->dst.cap : op->nslots);
+    if (!tiles) return 0;
+    if (shape != kOneGroup) blocks = mo_blocks((tiles + kMoThreads / 64 - 1) / (kMoThreads / 64));
+    if (shape != kTileDst) arg = tiles;
+  }
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kMoThreads), 0, hipStream_t(stream), *op, arg);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

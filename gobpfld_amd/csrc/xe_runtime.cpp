@@ -4310,36 +4310,42 @@ int mapop_current(xe_vm* vm, HostMap* m) {
   if (map_upload(vm, *m)) return fail(vm, XE_ERR_DEVICE, "map upload");
   return XE_OK;
 }
-int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, HostMap** mp, XeMapOp* op, xe_stream_t* sp) {
+// The table of a served map as the kernels read it.
+XeMapView map_view(const HostMap& m) {
+  XeMapView v{};
+  v.kind = m.dkind;
+  v.key_size = m.dkind == XE_DM_ARRAY ? 4 : m.def.key_size;
+  v.value_size = m.def.value_size;
+  v.max_entries = m.def.max_entries;
+  v.cap = m.cap;
+  v.kwords = m.kwords;
+  v.rwords = m.dkind == XE_DM_HASH ? xe_hash_rwords(m.kwords) : 0;
+  v.recs = m.d_keys;
+  v.vals = m.d_vals;
+  v.snap = m.d_snap;
+  v.count = m.d_count;
+  return v;
+}
+struct MapOpCall {
+  HostMap* m = nullptr;
+  XeMapOp o{};
+  xe_stream_t s = nullptr;
+};
+int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, MapOpCall& c) {
   if (!vm) return XE_ERR_INVAL;
   if (int rc = xe_sync(vm)) return rc;
-  HostMap* m = nullptr;
-  if (int rc = mapop_map(vm, mi, writes, &m)) return rc;
+  if (int rc = mapop_map(vm, mi, writes, &c.m)) return rc;
   if (count > kMoMaxCount) return fail(vm, XE_ERR_INVAL, "batched map operation: more than 2^31 keys");
   if (set_device(vm->settings.device)) return fail(vm, XE_ERR_DEVICE, "hipSetDevice failed");
-  xe_stream_t s = stream ? (xe_stream_t)stream : vm->stream;
-  *mp = m;
-  *sp = s;
+  c.s = stream ? (xe_stream_t)stream : vm->stream;
   if (!count) return 1;
-  if (int rc = mapop_current(vm, m)) return rc;
-  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(count) * 4) || dmemset(vm->d_mo, 0, kMoCounters * 4, s))
+  if (int rc = mapop_current(vm, c.m)) return rc;
+  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(count) * 4) || dmemset(vm->d_mo, 0, kMoCounters * 4, c.s))
     return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
-  XeMapOp o{};
-  o.kind = m->dkind;
-  o.key_size = m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size;
-  o.value_size = m->def.value_size;
-  o.max_entries = m->def.max_entries;
-  o.cap = m->cap;
-  o.kwords = m->kwords;
-  o.rwords = m->dkind == XE_DM_HASH ? xe_hash_rwords(m->kwords) : 0;
-  o.n = uint32_t(count);
-  o.recs = m->d_keys;
-  o.vals = m->d_vals;
-  o.snap = m->d_snap;
-  o.count = m->d_count;
-  o.ctr = (uint32_t*)vm->d_mo;
-  o.slot = o.ctr + kMoCounters;
-  *op = o;
+  static_cast<XeMapView&>(c.o) = map_view(*c.m);
+  c.o.n = uint32_t(count);
+  c.o.ctr = (uint32_t*)vm->d_mo;
+  c.o.slot = c.o.ctr + kMoCounters;
   return XE_OK;
 }
 int mapop_steps(xe_vm* vm, const XeMapOp& o, std::initializer_list<uint32_t> steps, xe_stream_t s) {
@@ -4347,16 +4353,70 @@ int mapop_steps(xe_vm* vm, const XeMapOp& o, std::initializer_list<uint32_t> ste
     if (xe_launch_mapop(&o, st, (void*)s)) return fail(vm, XE_ERR_DEVICE, "map operation launch");
   return XE_OK;
 }
+// A call wrote map m's device copy: the mirror reads the device again, the staged snapshots no longer match.
+void map_written(xe_vm* vm, HostMap* m) {
+  m->dev_dirty = true;
+  vm->staged_slot = -1;
+}
+// One visit to the host mirror rebuilds the table without its tombstones (map_download: drop_tombstones).
+int compact_via_host(xe_vm* vm, HostMap* m) {
+  if (map_download(vm, *m) || (m->host_dirty && map_upload(vm, *m))) return fail(vm, XE_ERR_DEVICE, "map compaction");
+  return XE_OK;
+}
+// The tile passes' scratch in vm->d_ms: the bitmap(s), the tile counts of each, the bins.
+int scan_scratch(xe_vm* vm, XeMapOp& o, size_t tiles, bool two_bitmaps, bool with_bins) {
+  const size_t maps = two_bitmaps ? 2 : 1;
+  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * maps * (kMsRounds * 8 + 4) + (with_bins ? kMtBins * 4 : 0)))
+    return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
+  o.bitmap = (uint64_t*)vm->d_ms;
+  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds * maps);
+  if (two_bitmaps) o.bitmap2 = o.bitmap + tiles * kMsRounds, o.tile2 = o.tile + tiles;
+  if (with_bins) o.bins = o.tile + tiles * maps;
+  return XE_OK;
+}
+// "width must be 1, 2, 4 or 8 and the field lies inside the value", said in the caller's words.
+struct FieldWords {
+  const char *width, *field, *value;
+};
+int check_field(xe_vm* vm, const FieldWords& what, uint32_t offset, uint32_t width, uint32_t value_size) {
+  if (width != 1 && width != 2 && width != 4 && width != 8) return fail(vm, XE_ERR_INVAL, std::string(what.width) + " must be 1, 2, 4 or 8");
+  if (uint64_t(offset) + width > value_size) return fail(vm, XE_ERR_INVAL, std::string(what.field) + " lies outside the " + what.value);
+  return XE_OK;
+}
+// LOCATE until the claims fit: the claims are made on map m's device copy and counted (*fresh; *cnt: the entries
+// before them), and put back (undo) when an ARRAY index is out of range (said with `range`) or the map is full
+// (`full`). Claims that fit under max_entries while a probe chain found no free record: deletes and unused keyed
+// reservations have left tombstones in all of them; the table is compacted through the host once and located
+// again (LOCATE writes kMoNew and kMoErr only).
+int claim_until_fits(xe_vm* vm, const XeMapOp& o, xe_stream_t s, uint32_t locate, uint32_t undo, HostMap* m, const char* what,
+                     const char* range, const char* full, uint32_t* cnt, uint32_t* fresh) {
+  const bool hash = m->dkind == XE_DM_HASH;
+  for (int attempt = 0;; attempt++) {
+    uint32_t ctr[kMoCounters];
+    if (int r = mapop_steps(vm, o, {locate}, s)) return r;
+    if (d2h(ctr, o.ctr, sizeof ctr, s) || (hash && d2h(cnt, m->d_count, 4, s)) || dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+    *fresh = ctr[kMoNew];
+    const bool fits = !hash || uint64_t(*cnt) + *fresh <= m->def.max_entries;
+    if (!ctr[kMoErr] && fits) return XE_OK;
+    if (int r = mapop_steps(vm, o, {undo}, s)) return r;
+    if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+    if (hash) m->dev_dirty = true;  // claims were written and put back: the mirror reads the device again
+    if (ctr[kMoErr] & kMoErrRange) return fail(vm, XE_ERR_INVAL, range);
+    if (!fits || attempt) return fail(vm, XE_ERR_NOMEM, full);
+    map_written(vm, m);
+    if (int r = compact_via_host(vm, m)) return r;
+    if (dmemset(o.ctr, 0, (kMoErr + 1) * 4, s)) return fail(vm, XE_ERR_DEVICE, what);
+  }
+}
 }  // namespace
 
 extern "C" {
 
 int xe_map_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_values, void* d_found,
                                void* stream) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  const int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, false, stream, &m, &o, &s);
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, false, stream, c);
   if (rc < 0) return rc;
   if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
   if (rc == 1) return XE_OK;
@@ -4371,10 +4431,9 @@ int xe_map_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64
 }
 
 int xe_map_update_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, const void* d_values, uint64_t count, void* stream) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, true, stream, &m, &o, &s);
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, true, stream, c);
   if (rc < 0) return rc;
   if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
   if (rc == 1) return XE_OK;
@@ -4386,40 +4445,20 @@ int xe_map_update_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, const 
       return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
   }
   o.win = m->d_win;
-  uint32_t ctr[kMoCounters], cnt = 0;
-  for (int attempt = 0;; attempt++) {
-    if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_LOCATE}, s)) return r;
-    if (d2h(ctr, o.ctr, sizeof ctr, s) || (m->dkind == XE_DM_HASH && d2h(&cnt, m->d_count, 4, s)) || dsync(s))
-      return fail(vm, XE_ERR_DEVICE, "map update batch");
-    const bool range = ctr[kMoErr] & kMoErrRange, full = ctr[kMoErr] & kMoErrFull;
-    const bool fits = m->dkind != XE_DM_HASH || uint64_t(cnt) + ctr[kMoNew] <= m->def.max_entries;
-    if (!range && !full && fits) break;
-    if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_UNDO}, s)) return r;
-    if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
-    if (m->dkind == XE_DM_HASH) m->dev_dirty = true;  // claims were written and put back: the mirror reads the device again
-    if (range) return fail(vm, XE_ERR_INVAL, "key out of range");
-    if (!fits || attempt) return fail(vm, XE_ERR_NOMEM, "map is full");
-    // The keys fit under max_entries but a probe chain found no free record: deletes and unused keyed
-    // reservations have left tombstones in all of them. One visit to the host mirror rebuilds the table
-    // without them (map_download: drop_tombstones); then the batch is located again.
-    m->dev_dirty = true;
-    vm->staged_slot = -1;
-    if (map_download(vm, *m) || (m->host_dirty && map_upload(vm, *m))) return fail(vm, XE_ERR_DEVICE, "map compaction");
-    if (dmemset(vm->d_mo, 0, kMoCounters * 4, s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
-  }
+  uint32_t cnt = 0, fresh = 0;
+  if (int r = claim_until_fits(vm, o, s, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, m, "map update batch", "key out of range", "map is full", &cnt, &fresh))
+    return r;
   if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY}, s)) return r;
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
-  if (m->dkind == XE_DM_HASH) m->live = cnt + ctr[kMoNew];
-  m->dev_dirty = true;
-  vm->staged_slot = -1;  // the device values changed under the staged snapshots
+  if (m->dkind == XE_DM_HASH) m->live = cnt + fresh;
+  map_written(vm, m);
   return XE_OK;
 }
 
 int xe_map_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_found, void* stream) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  const int rc = mapop_begin(vm, mi, d_keys ? count : 0, true, stream, &m, &o, &s);
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, d_keys ? count : 0, true, stream, c);
   if (rc < 0) return rc;
   if (m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
   if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
@@ -4430,40 +4469,45 @@ int xe_map_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64
   uint32_t cnt = 0;
   if (d2h(&cnt, m->d_count, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map delete batch");
   m->live = cnt;
-  m->dev_dirty = true;
-  vm->staged_slot = -1;
+  map_written(vm, m);
   return XE_OK;
 }
 
-// Host-pointer forms: stage, run the device form on the VM's stream, copy back.
+// Host-pointer forms: stage, run the device form on the VM's stream, copy back. A call the device form refuses
+// or has nothing to do for goes to it unstaged: its checks, its answer.
+//
+// The keys (and the values, if any) to d_mo_keys / d_mo_vals; d_mo_vals / d_mo_found made ready for the call's outputs.
+static int stage_in(xe_vm* vm, const HostMap* m, uint64_t count, const void* keys, const void* values, bool vals_out, bool found_out) {
+  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size), vb = size_t(count) * m->def.value_size;
+  set_device(vm->settings.device);
+  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ((values || vals_out) && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb)) ||
+      (found_out && ensure_buf(&vm->d_mo_found, &vm->d_mo_found_cap, size_t(count))) || h2d(vm->d_mo_keys, keys, kb, vm->stream) ||
+      (values && vb && h2d(vm->d_mo_vals, values, vb, vm->stream)) || dsync(vm->stream))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  return XE_OK;
+}
+// ... and the outputs back (either may be null).
+static int stage_out(xe_vm* vm, const HostMap* m, uint64_t count, void* values, uint8_t* found) {
+  const size_t vb = size_t(count) * m->def.value_size;
+  if ((values && vb && d2h(values, vm->d_mo_vals, vb, vm->stream)) || (found && d2h(found, vm->d_mo_found, size_t(count), vm->stream)) ||
+      ((values || found) && dsync(vm->stream)))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  return XE_OK;
+}
 int xe_map_lookup_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, void* values, uint8_t* found) {
   if (!vm) return XE_ERR_INVAL;
   HostMap* m = get_map(vm, mi);
-  if (!m || !count || !keys || !values || count > kMoMaxCount)
-    return xe_map_lookup_batch_device(vm, mi, keys, count, values, found, nullptr);  // its checks, its answer
-  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size), vb = size_t(count) * m->def.value_size;
-  set_device(vm->settings.device);
-  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb) ||
-      ensure_buf(&vm->d_mo_found, &vm->d_mo_found_cap, size_t(count)) || h2d(vm->d_mo_keys, keys, kb, vm->stream) ||
-      dsync(vm->stream))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (!m || !count || !keys || !values || count > kMoMaxCount) return xe_map_lookup_batch_device(vm, mi, keys, count, values, found, nullptr);
+  if (int rc = stage_in(vm, m, count, keys, nullptr, true, true)) return rc;
   if (int rc = xe_map_lookup_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_vals, vm->d_mo_found, nullptr)) return rc;
-  if ((vb && d2h(values, vm->d_mo_vals, vb, vm->stream)) || (found && d2h(found, vm->d_mo_found, size_t(count), vm->stream)) ||
-      dsync(vm->stream))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
-  return XE_OK;
+  return stage_out(vm, m, count, values, found);
 }
 
 int xe_map_update_batch_staged(xe_vm* vm, int32_t mi, const void* keys, const void* values, uint64_t count) {
   if (!vm) return XE_ERR_INVAL;
   HostMap* m = get_map(vm, mi);
-  if (!m || !count || !keys || !values || count > kMoMaxCount)
-    return xe_map_update_batch_device(vm, mi, keys, values, count, nullptr);
-  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size), vb = size_t(count) * m->def.value_size;
-  set_device(vm->settings.device);
-  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb) ||
-      h2d(vm->d_mo_keys, keys, kb, vm->stream) || (vb && h2d(vm->d_mo_vals, values, vb, vm->stream)) || dsync(vm->stream))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (!m || !count || !keys || !values || count > kMoMaxCount) return xe_map_update_batch_device(vm, mi, keys, values, count, nullptr);
+  if (int rc = stage_in(vm, m, count, keys, values, false, false)) return rc;
   return xe_map_update_batch_device(vm, mi, vm->d_mo_keys, vm->d_mo_vals, count, nullptr);
 }
 
@@ -4471,15 +4515,9 @@ int xe_map_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count,
   if (!vm) return XE_ERR_INVAL;
   HostMap* m = get_map(vm, mi);
   if (!m || !count || !keys || count > kMoMaxCount) return xe_map_delete_batch_device(vm, mi, keys, count, found, nullptr);
-  const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size);
-  set_device(vm->settings.device);
-  if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ensure_buf(&vm->d_mo_found, &vm->d_mo_found_cap, size_t(count)) ||
-      h2d(vm->d_mo_keys, keys, kb, vm->stream) || dsync(vm->stream))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (int rc = stage_in(vm, m, count, keys, nullptr, false, true)) return rc;
   if (int rc = xe_map_delete_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_found, nullptr)) return rc;
-  if (found && (d2h(found, vm->d_mo_found, size_t(count), vm->stream) || dsync(vm->stream)))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
-  return XE_OK;
+  return stage_out(vm, m, count, nullptr, found);
 }
 
 // Scan and expire (xe_mapops.h SELECT .. EXPIRE). host: keys / values are host memory, staged through
@@ -4493,8 +4531,7 @@ static int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp
   if (f->op >= kMfOps) return fail(vm, XE_ERR_INVAL, "map filter: unknown op");
   if (f->pad) return fail(vm, XE_ERR_INVAL, "map filter: pad must be 0");
   if (f->op != XE_MF_ALL) {
-    if (f->width != 1 && f->width != 2 && f->width != 4 && f->width != 8) return fail(vm, XE_ERR_INVAL, "map filter: width must be 1, 2, 4 or 8");
-    if (uint64_t(f->offset) + f->width > m->def.value_size) return fail(vm, XE_ERR_INVAL, "map filter: the field lies outside the value");
+    if (int e = check_field(vm, {"map filter: width", "map filter: the field", "value"}, f->offset, f->width, m->def.value_size)) return e;
     o.f_off = f->offset;
     o.f_width = f->width;
     o.f_operand = f->operand;
@@ -4533,17 +4570,15 @@ static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uin
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
   if (remove) {
     m->live = cnt;
-    m->dev_dirty = true;
-    vm->staged_slot = -1;
+    map_written(vm, m);
   }
   return XE_OK;
 }
 static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
                         uint64_t* matched, void* stream, bool expire, bool host) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  const int rc = mapop_begin(vm, mi, 1, expire, host ? nullptr : stream, &m, &o, &s);  // (the counters; slots come with r)
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, 1, expire, host ? nullptr : stream, c);  // (the counters; slots come with r)
   if (rc < 0) return rc;
   if (expire && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
   if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
@@ -4551,9 +4586,7 @@ static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* key
   *matched = 0;
   const size_t tiles = xe_ms_tiles(o.nslots);
   if (!tiles) return XE_OK;
-  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
-  o.bitmap = (uint64_t*)vm->d_ms;
-  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds);
+  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
   if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
   uint32_t total = 0;
   if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map scan");
@@ -4566,10 +4599,9 @@ static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* key
 // queued without a readback; the counters then give matched, the cut and r in one copy.
 static int map_order_check(xe_vm* vm, HostMap* m, const xe_map_order* ord, XeMapOp& o) {
   if (!ord) return fail(vm, XE_ERR_INVAL, "null map order");
-  if (ord->width != 1 && ord->width != 2 && ord->width != 4 && ord->width != 8) return fail(vm, XE_ERR_INVAL, "map order: width must be 1, 2, 4 or 8");
+  if (int e = check_field(vm, {"map order: width", "map order: the field", "value"}, ord->offset, ord->width, m->def.value_size)) return e;
   if (ord->pad) return fail(vm, XE_ERR_INVAL, "map order: pad must be 0");
   if (ord->descending > 1) return fail(vm, XE_ERR_INVAL, "map order: descending must be 0 or 1");
-  if (uint64_t(ord->offset) + ord->width > m->def.value_size) return fail(vm, XE_ERR_INVAL, "map order: the field lies outside the value");
   o.t_off = ord->offset;
   o.t_width = ord->width;
   o.t_desc = ord->descending;
@@ -4577,10 +4609,9 @@ static int map_order_check(xe_vm* vm, HostMap* m, const xe_map_order* ord, XeMap
 }
 static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
                        uint64_t* matched, uint64_t* cut, void* stream, bool evict, bool host) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  const int rc = mapop_begin(vm, mi, 1, evict, host ? nullptr : stream, &m, &o, &s);
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, 1, evict, host ? nullptr : stream, c);
   if (rc < 0) return rc;
   if (evict && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
   if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
@@ -4590,13 +4621,7 @@ static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_m
   if (cut) *cut = 0;
   const size_t tiles = xe_ms_tiles(o.nslots);
   if (!tiles) return XE_OK;
-  // two bitmaps, two tile-count arrays, the bins
-  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * 2 * (kMsRounds * 8 + 4) + kMtBins * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
-  o.bitmap = (uint64_t*)vm->d_ms;
-  o.bitmap2 = o.bitmap + tiles * kMsRounds;
-  o.tile = (uint32_t*)(o.bitmap2 + tiles * kMsRounds);
-  o.tile2 = o.tile + tiles;
-  o.bins = o.tile2 + tiles;
+  if (int e = scan_scratch(vm, o, tiles, true, true)) return e;
   o.t_k = uint32_t(std::min<uint64_t>(k, 0xffffffffu));  // (more than any table holds)
   if (dmemset(o.bins, 0, kMtBins * 4, s)) return fail(vm, XE_ERR_DEVICE, "map top");
   for (o.t_pass = 0; o.t_pass < o.t_width; o.t_pass++)
@@ -4617,10 +4642,9 @@ static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_m
   return map_scan_report(vm, m, o, s, r, keys, values, evict, host, evict ? "map evict" : "map top");
 }
 static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  const int rc = mapop_begin(vm, mi, 1, false, stream, &m, &o, &s);
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, 1, false, stream, c);
   if (rc < 0) return rc;
   if (!out) return fail(vm, XE_ERR_INVAL, "null stats");
   if (int e = map_scan_setup(vm, m, f, o)) return e;
@@ -4638,8 +4662,8 @@ static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe
   return XE_OK;
 }
 
-// Group (xe_mapops.h SELECT, SCAN on the source, then LOCATE .. ADD): the update's locate / undo / compact /
-// retry loop with the claims made by the source's selected slots. Nothing per entry is allocated.
+// Group (xe_mapops.h SELECT, SCAN on the source, then LOCATE .. ADD): the update's claim_until_fits with the
+// claims made by the source's selected slots. Nothing per entry is allocated.
 static int map_group_check(xe_vm* vm, const HostMap* sm, const HostMap* dm, const xe_map_group_spec* g) {
   if (g->from > XE_MG_VALUE) return fail(vm, XE_ERR_INVAL, "map group: from must be XE_MG_KEY or XE_MG_VALUE");
   if (g->pad) return fail(vm, XE_ERR_INVAL, "map group: pad must be 0");
@@ -4655,10 +4679,8 @@ static int map_group_check(xe_vm* vm, const HostMap* sm, const HostMap* dm, cons
   if (g->count_off == XE_MG_NONE && g->sum_off == XE_MG_NONE) return fail(vm, XE_ERR_INVAL, "map group: no accumulator");
   if (g->sum_off != XE_MG_NONE && !g->measure_width) return fail(vm, XE_ERR_INVAL, "map group: a sum needs a measure");
   if (g->measure_width) {
-    if (g->measure_width != 1 && g->measure_width != 2 && g->measure_width != 4 && g->measure_width != 8)
-      return fail(vm, XE_ERR_INVAL, "map group: measure width must be 1, 2, 4 or 8");
-    if (uint64_t(g->measure_off) + g->measure_width > sm->def.value_size)
-      return fail(vm, XE_ERR_INVAL, "map group: the measure lies outside the source value");
+    if (int e = check_field(vm, {"map group: measure width", "map group: the measure", "source value"}, g->measure_off, g->measure_width, sm->def.value_size))
+      return e;
   }
   if (dm->def.value_size & 7) return fail(vm, XE_ERR_INVAL, "map group: the destination's value_size must be a multiple of 8");
   for (uint32_t off : {g->count_off, g->sum_off})
@@ -4678,26 +4700,17 @@ static int map_group_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const x
   if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
   if (src == dst) return fail(vm, XE_ERR_INVAL, "map group: source and destination are one map");
   if (int rc = map_group_check(vm, sm, dm, g)) return rc;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
-  if (int rc = mapop_begin(vm, src, 1, false, stream, &sm, &o, &s)) return rc;  // (the counters; no per-entry slots)
-  if (int e = map_scan_setup(vm, sm, f, o)) return e;
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  if (int rc = mapop_begin(vm, src, 1, false, stream, c)) return rc;  // (the counters; no per-entry slots)
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
   if (int rc = mapop_current(vm, dm)) return rc;
   *matched = 0;
   if (created) *created = 0;
   const size_t tiles = xe_ms_tiles(o.nslots);
   if (!tiles) return XE_OK;
-  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
-  o.bitmap = (uint64_t*)vm->d_ms;
-  o.tile = (uint32_t*)(o.bitmap + tiles * kMsRounds);
-  const bool hash = dm->dkind == XE_DM_HASH;
-  o.g_kind = dm->dkind;
-  o.g_key_size = hash ? dm->def.key_size : 4;
-  o.g_value_size = dm->def.value_size;
-  o.g_max_entries = dm->def.max_entries;
-  o.g_cap = dm->cap;
-  o.g_kwords = dm->kwords;
-  o.g_rwords = hash ? xe_hash_rwords(dm->kwords) : 0;
+  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  o.dst = map_view(*dm);
   o.g_from = g->from;
   o.g_off = g->offset;
   o.g_len = g->len;
@@ -4705,42 +4718,22 @@ static int map_group_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const x
   o.g_mwidth = g->measure_width;
   o.g_count_off = g->count_off;
   o.g_sum_off = g->sum_off;
-  o.g_recs = dm->d_keys;
-  o.g_vals = dm->d_vals;
-  o.g_snap = dm->d_snap;
-  o.g_count = dm->d_count;
   if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
   uint32_t total = 0;
   if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
   *matched = total;
   if (!total) return XE_OK;
-  uint32_t ctr[kMoCounters], cnt = 0;
-  for (int attempt = 0;; attempt++) {
-    if (int r = mapop_steps(vm, o, {XE_MO_GROUP_LOCATE}, s)) return r;
-    if (d2h(ctr, o.ctr, sizeof ctr, s) || (hash && d2h(&cnt, dm->d_count, 4, s)) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
-    const bool range = ctr[kMoErr] & kMoErrRange, full = ctr[kMoErr] & kMoErrFull;
-    const bool fits = !hash || uint64_t(cnt) + ctr[kMoNew] <= dm->def.max_entries;
-    if (!range && !full && fits) break;
-    if (int r = mapop_steps(vm, o, {XE_MO_GROUP_UNDO}, s)) return r;
-    if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
-    if (hash) dm->dev_dirty = true;  // claims were written and put back: the mirror reads the device again
-    if (range) return fail(vm, XE_ERR_INVAL, "map group: a group's index is out of the destination's range");
-    if (!fits || attempt) return fail(vm, XE_ERR_NOMEM, "map group: the destination is full");
-    // the groups fit under max_entries but a probe chain has no free record left: one compaction through the
-    // host, as xe_map_update_batch_device makes it; the claims and the error are counted again
-    dm->dev_dirty = true;
-    vm->staged_slot = -1;
-    if (map_download(vm, *dm) || (dm->host_dirty && map_upload(vm, *dm))) return fail(vm, XE_ERR_DEVICE, "map compaction");
-    if (dmemset(o.ctr, 0, (kMoErr + 1) * 4, s)) return fail(vm, XE_ERR_DEVICE, "map group");
-  }
+  uint32_t cnt = 0, fresh = 0;
+  if (int r = claim_until_fits(vm, o, s, XE_MO_GROUP_LOCATE, XE_MO_GROUP_UNDO, dm, "map group",
+                               "map group: a group's index is out of the destination's range", "map group: the destination is full", &cnt, &fresh))
+    return r;
   if (int r = mapop_steps(vm, o, {XE_MO_GROUP_PUBLISH, XE_MO_GROUP_ADD}, s)) return r;
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map group");
-  if (hash) {
-    dm->live = cnt + ctr[kMoNew];
-    if (created) *created = ctr[kMoNew];
+  if (dm->dkind == XE_DM_HASH) {
+    dm->live = cnt + fresh;
+    if (created) *created = fresh;
   }
-  dm->dev_dirty = true;
-  vm->staged_slot = -1;  // the device values changed under the staged snapshots
+  map_written(vm, dm);
   return XE_OK;
 }
 
@@ -4753,11 +4746,10 @@ int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_ma
 // written; no free record: no run has a start) and after REBUILD (a run too long for one lane). Both of these
 // tables take the route through the host mirror that xe_map_update_batch_device takes for a full probe chain.
 int xe_map_compact(xe_vm* vm, int32_t mi, uint32_t flags, xe_map_compact_info* info, void* stream) {
-  HostMap* m = nullptr;
-  XeMapOp o{};
-  xe_stream_t s = nullptr;
+  MapOpCall c;
+  auto& [m, o, s] = c;
   const bool only = flags & XE_MC_COUNT_ONLY;
-  const int rc = mapop_begin(vm, mi, 1, !only, stream, &m, &o, &s);  // (the counters)
+  const int rc = mapop_begin(vm, mi, 1, !only, stream, c);  // (the counters)
   if (rc < 0) return rc;
   if (!info) return fail(vm, XE_ERR_INVAL, "null compact info");
   if (flags & ~XE_MC_COUNT_ONLY) return fail(vm, XE_ERR_INVAL, "map compact: unknown flag");
@@ -4765,12 +4757,7 @@ int xe_map_compact(xe_vm* vm, int32_t mi, uint32_t flags, xe_map_compact_info* i
   if (m->dkind != XE_DM_HASH) return XE_OK;  // an ARRAY has no tombstones
   o.nslots = m->cap;
   o.c_only = only;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (ensure_buf(&vm->d_ms, &vm->d_ms_cap, tiles * 2 * (kMsRounds * 8 + 4))) return fail(vm, XE_ERR_DEVICE, "device alloc (map scan scratch)");
-  o.bitmap = (uint64_t*)vm->d_ms;
-  o.bitmap2 = o.bitmap + tiles * kMsRounds;
-  o.tile = (uint32_t*)(o.bitmap2 + tiles * kMsRounds);
-  o.tile2 = o.tile + tiles;
+  if (int e = scan_scratch(vm, o, xe_ms_tiles(o.nslots), true, false)) return e;
   if (int r = mapop_steps(vm, o, {XE_MO_COMPACT_MARK, XE_MO_SCAN_SCAN}, s)) return r;
   uint32_t ctr[kMoCounters];
   if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map compact");
@@ -4786,10 +4773,9 @@ int xe_map_compact(xe_vm* vm, int32_t mi, uint32_t flags, xe_map_compact_info* i
     host = ctr[kMcLong] != 0;
   }
   if (only) return XE_OK;
-  m->dev_dirty = true;
-  vm->staged_slot = -1;  // the device values moved under the staged snapshots
+  map_written(vm, m);
   if (host) {
-    if (map_download(vm, *m) || (m->host_dirty && map_upload(vm, *m))) return fail(vm, XE_ERR_DEVICE, "map compaction");
+    if (int r = compact_via_host(vm, m)) return r;
     info->via_host = 1;
   } else {
     info->moved = ctr[kMcMoved];
