@@ -1,6 +1,7 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
 // xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device,
-// xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group, xe_map_compact): the per-key and per-slot decision logic that the kernels
+// xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group, xe_map_compact, xe_map_modify_device,
+// xe_map_modify_batch_device): the per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
 // declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
 //
@@ -97,6 +98,21 @@
 //                    is longer than kMcMaxRun is left alone and flagged (kMcLong): the runtime then compacts
 //                    through the host. The longest run with a tombstone is an atomic max; with c_only the pass
 //                    only measures
+//   modify   TILE    (the silent, uncapped walk of values up to kMmTileMax bytes: every match is edited and none
+//                    reported) one tile pass in the SELECT shape: a lane evaluates the filter on its slot and
+//                    edits the value where it lies: a nil-backed (VLEN0) value is zeroed first, the edits run in
+//                    list order on the value as it stands, the whole value goes to the delta base and the
+//                    record becomes plain FULL. The matches are counted by ballot (kMoMatched). No bitmap, no
+//                    SCAN, no SCATTER, no per-entry scratch
+//            SELECT, SCAN, SCATTER, COPY   (the general walk: the scan's; COPY reports the values from before)
+//            EDIT    a sub-group per reported entry j < r over slot[j]: TILE's edit of one slot, the value shared
+//                    by the sub-group's lanes (mm_modify_item says what orders their stores)
+//   modify   FIND    the lookup's FIND and VALUE when the old values are wanted, the delete's FIND otherwise:
+//   (keyed)          found[i], slot[i] and the values from before, complete before any edit
+//            MARK    every present entry raises its slot's last-writer word to i + 1 (update MARK's atomic max):
+//                    one of a key's repetitions is named, decided before any value byte moves
+//            KEYED   a sub-group per entry; the one whose i + 1 is still there edits the slot as EDIT does and
+//                    clears the word: each distinct present key is edited exactly once
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
 // an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
@@ -124,6 +140,7 @@ enum : uint32_t {
   XE_MO_TOP_PREFIX, XE_MO_TOP_PICK, XE_MO_TOP_CUT, XE_MO_TOP_TRIM, XE_MO_TOP_STATS,
   XE_MO_GROUP_LOCATE, XE_MO_GROUP_UNDO, XE_MO_GROUP_PUBLISH, XE_MO_GROUP_ADD,
   XE_MO_COMPACT_MARK, XE_MO_COMPACT_REBUILD,
+  XE_MO_MODIFY_TILE, XE_MO_MODIFY_EDIT, XE_MO_MODIFY_MARK, XE_MO_MODIFY_KEYED,
   XE_MO_STEPS
 };
 
@@ -152,6 +169,11 @@ constexpr uint32_t kMgLeaders = XE_MG_LEADERS, kMgNone = 0xffffffffu;
 // longer than kMcMaxRun" (counters); kMcMaxRun bounds the records one lane walks alone (DESIGN.md has the walk's
 // measured time); kMcDead: the record at a run offset is no entry
 constexpr uint32_t kMcFree = 4, kMcMoved = 5, kMcLongest = 6, kMcLong = 7, kMcMaxRun = 4096, kMcDead = 0xffffffffu;
+// modify: the edit's ops (include/xdpemu.h XE_MM_*); the silent uncapped walk edits values of up to kMmTileMax
+// bytes on their slot's lane (MODIFY_TILE), larger ones go the general way where a sub-group shares a value
+enum : uint32_t { kMmSet = 0, kMmAdd, kMmSub, kMmAddSat, kMmSubSat, kMmAnd, kMmOr, kMmXor, kMmMin, kMmMax, kMmShr, kMmOps };
+constexpr uint32_t kMmTileMax = 64;
+static_assert(kMmTileMax >= kMoInline, "the single pass serves at least the values that move on one lane");
 // the filter's ops (include/xdpemu.h XE_MF_*)
 enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
 
@@ -193,7 +215,13 @@ struct XeMapOp : XeMapView {
   uint32_t g_count_off, g_sum_off;   // the accumulators in the destination value (kMgNone: none)
   // compact
   uint32_t c_only;        // 1: REBUILD measures and changes nothing
+  // modify
+  uint32_t m_n;           // the edits in use
+  xe_map_edit m_edits[XE_MM_MAX_EDITS];  // checked by the runtime: op, width, the field and an operand field inside the value
 };
+// The whole struct is a kernel argument. The edits add 200 bytes; it stays far below the 4 KiB a HIP kernel's
+// arguments may take.
+static_assert(sizeof(XeMapOp) <= 1024, "XeMapOp is passed by value to every map-operation kernel");
 XE_HD uint32_t xe_ms_tiles(uint32_t nslots) { return (nslots + kMsTile - 1) / kMsTile; }
 
 // lanes that share one value (a power of two <= 64)
@@ -822,6 +850,96 @@ XE_HD bool mc_run_counts(const XeMapOp& o, uint32_t len, uint32_t first) {
   return !o.c_only;
 }
 
+// ---------------------------------------------------------------- modify
+// One edit's arithmetic on the zero-extended field (include/xdpemu.h XE_MM_*): the new field, within the width.
+XE_HD uint64_t mm_apply(uint32_t op, uint64_t field, uint64_t operand, uint32_t width) {
+  const uint64_t mask = mt_mask(width);
+  const uint64_t sat = operand > mask ? mask : operand;  // an operand the field cannot hold acts as the largest it can
+  switch (op) {
+    case kMmSet: return operand & mask;
+    case kMmAdd: return (field + operand) & mask;
+    case kMmSub: return (field - operand) & mask;
+    case kMmAddSat: return sat > mask - field ? mask : field + sat;
+    case kMmSubSat: return field > sat ? field - sat : 0;
+    case kMmAnd: return field & operand;
+    case kMmOr: return (field | operand) & mask;
+    case kMmXor: return (field ^ operand) & mask;
+    case kMmMin: return field < sat ? field : sat;
+    case kMmMax: return field > sat ? field : sat;
+    case kMmShr: return operand >= 8 * width ? 0 : field >> operand;
+    default: return field;
+  }
+}
+// The field at v set to x: one store where the address allows it (ms_field's counterpart), else bytes.
+XE_HD void mm_store(uint8_t* v, uint32_t width, uint64_t x) {
+  if (!(uintptr_t(v) & (width - 1))) {
+    if (width == 8) *reinterpret_cast<uint64_t*>(v) = x;
+    else if (width == 4) *reinterpret_cast<uint32_t*>(v) = uint32_t(x);
+    else if (width == 2) *reinterpret_cast<uint16_t*>(v) = uint16_t(x);
+    else *v = uint8_t(x);
+    return;
+  }
+  for (uint32_t b = 0; b < 8; b++)
+    if (b < width) v[b] = uint8_t(x >> (8 * b));
+}
+// The edit list applied to the value at v, by one lane, in list order on the value as it stands (zero: it reads
+// as zeros, so it is zeroed first). An operand field is read when its edit runs.
+XE_HD void mm_edit_value(const XeMapOp& o, uint8_t* v, bool zero) {
+  if (zero) mo_move(v, nullptr, o.value_size, 0, 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1  // (an edit's words are read when its turn comes: the list is not held in registers)
+#endif
+  for (uint32_t e = 0; e < o.m_n; e++) {
+    const xe_map_edit& d = o.m_edits[e];
+    const uint64_t operand = (d.flags & XE_MM_OPERAND_FIELD) ? ms_field(v + d.operand, d.width) : d.operand;
+    mm_store(v + d.offset, d.width, mm_apply(d.op, ms_field(v + d.offset, d.width), operand, d.width));
+  }
+}
+// What orders the stores of one lane before the loads and stores of the other lanes of its sub-group. A
+// sub-group never spans waves (xe_mo_lanes <= 64 divides the wave), and a wave's vector memory instructions
+// reach the memory pipeline in program order: release and acquire fences at wavefront scope keep the compiler
+// from moving accesses across this point and are all the AMDGPU memory model asks for between the lanes of one
+// wave. Nothing here depends on the lanes running in lockstep.
+XE_HD void mm_subgroup_order() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
+}
+// Slot `slot` (sbase included) edited by lane `sub` of the `lanes` that share it: a nil-backed value is zeroed,
+// the edits run, the whole value goes to the delta base (so xe_map_delta sees no packet adds on it, and adds
+// still pending are dropped, as an update drops them), the record is left plain FULL (HASH: VLEN0 and the
+// last-writer word cleared; keyed, ARRAY: the index's last-writer word cleared).
+// Lane 0 alone zeroes and edits the value in the map: one thread's stores and loads to one address keep their
+// order. The copy to the delta base is shared, so the other lanes read bytes lane 0 wrote: mm_subgroup_order
+// stands between the two. The record's word 0 is written by lane 0 after every lane of the sub-group has read
+// it (the read below is in front of the ordering point, the write behind it).
+XE_HD void mm_modify_item(const XeMapOp& o, uint32_t slot, uint32_t sub, uint32_t lanes, bool keyed) {
+  uint64_t* r = o.kind == XE_DM_HASH ? o.recs + uint64_t(slot) * o.rwords : nullptr;
+  const uint64_t w0 = r ? r[0] : 0;
+  uint8_t* v = o.vals + uint64_t(slot) * o.value_size;
+  if (sub == 0) mm_edit_value(o, v, (uint32_t(w0) & XE_SLOT_VLEN0) != 0);
+  if (lanes > 1) mm_subgroup_order();
+  mo_move(o.snap + uint64_t(slot) * o.value_size, v, o.value_size, sub, lanes);
+  if (sub != 0) return;
+  if (r) {
+    if (w0 != XE_SLOT_FULL) r[0] = XE_SLOT_FULL;
+  } else if (keyed) {
+    o.win[slot] = 0;
+  }
+}
+// MARK: a present entry names itself on its slot; KEYED: the entry still named there edits the slot.
+XE_HD void mm_mark_item(const XeMapOp& o, uint32_t i) {
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (s != kMoAbsent) mo_hi_max(o, s, i + 1);
+}
+XE_HD void mm_keyed_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint32_t lanes) {
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (s == kMoAbsent || mo_hi_get(o, s) != i + 1) return;  // absent, or another repetition of the key edits
+  mm_modify_item(o, s, sub, lanes, true);
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
@@ -982,6 +1100,11 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
     }
     return 0;
   }
+  if (step == XE_MO_MODIFY_TILE) {
+    for (uint32_t s = 0; s < o.nslots; s++)
+      if (ms_select_item(o, s)) mm_modify_item(o, o.sbase + s, 0, 1, false), o.ctr[kMoMatched]++;
+    return 0;
+  }
   for (uint32_t i = 0; i < o.n; i++) {
     switch (step) {
       case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i, mo_find), true); break;
@@ -995,6 +1118,9 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
       case XE_MO_DELETE_ZERO: mo_delete_zero_item(o, i, 0, 1); break;
       case XE_MO_SCAN_COPY: ms_copy_item(o, i, 0, 1); break;
       case XE_MO_SCAN_EXPIRE: ms_expire_item(o, i, 0, 1); break;
+      case XE_MO_MODIFY_EDIT: mm_modify_item(o, o.slot[i], 0, 1, false); break;
+      case XE_MO_MODIFY_MARK: mm_mark_item(o, i); break;
+      case XE_MO_MODIFY_KEYED: mm_keyed_item(o, i, 0, 1); break;
       default: return -1;
     }
   }

@@ -1,4 +1,4 @@
-// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group, compact (xe_mapops.h:
+// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group, compact, modify (xe_mapops.h:
 // the steps and what each one decides). One kernel per step; a step works either one batch entry per lane
 // (probes, claims, marks) or one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
 // destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
@@ -93,6 +93,7 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_lane_kernel(XeMapOp o, ui
         case XE_MO_UPDATE_UNDO: mo_update_undo_item(o, i); break;
         case XE_MO_UPDATE_MARK: mo_update_mark_item(o, i); break;
         case XE_MO_DELETE_CLAIM: mo_delete_claim_item(o, i); break;
+        case XE_MO_MODIFY_MARK: mm_mark_item(o, i); break;
         default: break;
       }
     }
@@ -112,6 +113,8 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_value_kernel(XeMapOp o, u
       case XE_MO_DELETE_ZERO: mo_delete_zero_item(o, uint32_t(i), sub, LANES); break;
       case XE_MO_SCAN_COPY: ms_copy_item(o, uint32_t(i), sub, LANES); break;
       case XE_MO_SCAN_EXPIRE: ms_expire_item(o, uint32_t(i), sub, LANES); break;
+      case XE_MO_MODIFY_EDIT: mm_modify_item(o, o.slot[i], sub, LANES, false); break;
+      case XE_MO_MODIFY_KEYED: mm_keyed_item(o, uint32_t(i), sub, LANES); break;
       default: break;
     }
   }
@@ -489,6 +492,29 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapcompact_rebuild_kernel(XeMap
   });
 }
 
+// ---- modify. TILE has SELECT's shape: the filter of the four rounds first (their loads are in flight
+// together), then a selected slot's lane edits its value where it lies (mm_modify_item with the lane alone: no
+// store of one lane meets another's). The ballot takes the whole wave: a lane whose slot lies past the table
+// votes "not selected". The wave's matches are counted once, after its last tile.
+__global__ void __launch_bounds__(kMoThreads) xe_mapmodify_tile_kernel(XeMapOp o, uint32_t tiles) {
+  uint32_t cnt = 0;
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
+    uint32_t hit = 0;  // bit r: the slot of round r is selected
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = tile_slot(t, r, lane);
+      hit |= uint32_t(s < o.nslots && ms_select_item(o, s)) << r;
+    }
+#pragma unroll 1  // (one copy of the edit's code)
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const bool mine = (hit >> r) & 1;
+      cnt += uint32_t(__popcll(__ballot(mine)));
+      if (mine) mm_modify_item(o, o.sbase + tile_slot(t, r, lane), 0, 1, false);
+    }
+  });
+  if ((threadIdx.x & 63) == 0 && cnt) mo_add32(o.ctr + kMoMatched, cnt);
+}
+
 // The steps: how each is launched, and its kernel. kLane / kValue: one batch entry per lane / per sub-group of
 // xe_mo_lanes lanes (the kernel's second argument is the step; a value step's kernel is the instantiation for
 // those lanes). kTileSrc / kTileDst: a wave per tile of the source's slots (the second argument is their
@@ -505,9 +531,12 @@ struct MoTable {
 };
 constexpr MoTable mo_table() {
   MoTable t{};
-  for (uint32_t s : {XE_MO_LOOKUP_FIND, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM})
+  for (uint32_t s : {XE_MO_LOOKUP_FIND, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM,
+                     XE_MO_MODIFY_MARK})
     t.row[s] = {kLane, xe_mapop_lane_kernel};
-  for (uint32_t s : {XE_MO_LOOKUP_VALUE, XE_MO_UPDATE_COPY, XE_MO_DELETE_ZERO, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE}) t.row[s] = {kValue, nullptr};
+  for (uint32_t s : {XE_MO_LOOKUP_VALUE, XE_MO_UPDATE_COPY, XE_MO_DELETE_ZERO, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE, XE_MO_MODIFY_EDIT,
+                     XE_MO_MODIFY_KEYED})
+    t.row[s] = {kValue, nullptr};
   t.row[XE_MO_SCAN_SELECT] = {kTileSrc, xe_mapscan_select_kernel};
   t.row[XE_MO_SCAN_SCAN] = {kOneGroup, xe_mapscan_scan_kernel};
   t.row[XE_MO_SCAN_SCATTER] = {kTileSrc, xe_mapscan_scatter_kernel};
@@ -521,6 +550,7 @@ constexpr MoTable mo_table() {
   t.row[XE_MO_GROUP_ADD] = {kTileSrc, xe_mapgroup_add_kernel};
   t.row[XE_MO_COMPACT_MARK] = {kTileSrc, xe_mapcompact_mark_kernel};
   t.row[XE_MO_COMPACT_REBUILD] = {kTileSrc, xe_mapcompact_rebuild_kernel};
+  t.row[XE_MO_MODIFY_TILE] = {kTileSrc, xe_mapmodify_tile_kernel};
   return t;
 }
 constexpr MoTable kMoSteps = mo_table();

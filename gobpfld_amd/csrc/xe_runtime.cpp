@@ -4383,6 +4383,16 @@ int check_field(xe_vm* vm, const FieldWords& what, uint32_t offset, uint32_t wid
   if (uint64_t(offset) + width > value_size) return fail(vm, XE_ERR_INVAL, std::string(what.field) + " lies outside the " + what.value);
   return XE_OK;
 }
+// An ARRAY map's last-writer words (xe_mapops.h), allocated at the first call that marks: zero between calls.
+int array_win(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s) {
+  if (m->dkind == XE_DM_ARRAY && !m->d_win) {
+    if (dev_alloc((void**)&m->d_win, size_t(std::max<uint32_t>(m->def.max_entries, 1)) * 4) ||
+        dmemset(m->d_win, 0, size_t(std::max<uint32_t>(m->def.max_entries, 1)) * 4, s))
+      return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  }
+  o.win = m->d_win;
+  return XE_OK;
+}
 // LOCATE until the claims fit: the claims are made on map m's device copy and counted (*fresh; *cnt: the entries
 // before them), and put back (undo) when an ARRAY index is out of range (said with `range`) or the map is full
 // (`full`). Claims that fit under max_entries while a probe chain found no free record: deletes and unused keyed
@@ -4439,12 +4449,7 @@ int xe_map_update_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, const 
   if (rc == 1) return XE_OK;
   o.keys = (const uint8_t*)d_keys;
   o.values_in = (const uint8_t*)d_values;
-  if (m->dkind == XE_DM_ARRAY && !m->d_win) {
-    if (dev_alloc((void**)&m->d_win, size_t(std::max<uint32_t>(m->def.max_entries, 1)) * 4) ||
-        dmemset(m->d_win, 0, size_t(std::max<uint32_t>(m->def.max_entries, 1)) * 4, s))
-      return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
-  }
-  o.win = m->d_win;
+  if (int r = array_win(vm, m, o, s)) return r;
   uint32_t cnt = 0, fresh = 0;
   if (int r = claim_until_fits(vm, o, s, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, m, "map update batch", "key out of range", "map is full", &cnt, &fresh))
     return r;
@@ -4542,12 +4547,13 @@ static int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp
   else o.nslots = m->cap;
   return XE_OK;
 }
-// The r entries the bitmap and the tile bases select: SCATTER, COPY, (remove) EXPIRE, the staging back to
-// the host, the synchronisation and the host's view of a map that lost entries.
-static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uint32_t r, void* keys, void* values, bool remove,
+// The r entries the bitmap and the tile bases select: SCATTER, COPY, the step `after` on the same entries
+// (XE_MO_SCAN_EXPIRE removes them, XE_MO_MODIFY_EDIT edits them, XE_MO_STEPS: none), the staging back to the
+// host, the synchronisation and the host's view of a map that lost entries or was written.
+static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uint32_t r, void* keys, void* values, uint32_t after,
                            bool host, const char* what) {
-  const bool out = keys || values;
-  if (!r || (!remove && !out)) return XE_OK;
+  const bool out = keys || values, remove = after == XE_MO_SCAN_EXPIRE, modify = after == XE_MO_MODIFY_EDIT;
+  if (!r || (!remove && !modify && !out)) return XE_OK;
   const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size;
   if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
   o.ctr = (uint32_t*)vm->d_mo;
@@ -4565,13 +4571,13 @@ static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uin
     if (int e = mapop_steps(vm, o, {XE_MO_SCAN_EXPIRE}, s)) return e;
     if (d2h(&cnt, m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, what);
   }
+  if (modify)
+    if (int e = mapop_steps(vm, o, {XE_MO_MODIFY_EDIT}, s)) return e;
   if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s))))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
-  if (remove) {
-    m->live = cnt;
-    map_written(vm, m);
-  }
+  if (remove) m->live = cnt;
+  if (remove || modify) map_written(vm, m);
   return XE_OK;
 }
 static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
@@ -4591,8 +4597,8 @@ static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* key
   uint32_t total = 0;
   if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map scan");
   *matched = total;
-  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), keys, values, expire, host,
-                         expire ? "map expire" : "map scan");
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), keys, values,
+                         expire ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, host, expire ? "map expire" : "map scan");
 }
 
 // Top and evict (xe_mapops.h PREFIX .. TRIM, then the scan's steps): everything up to the final SCAN is
@@ -4639,7 +4645,7 @@ static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_m
     const uint64_t key = uint64_t(ctr[kMtPrefix]) | uint64_t(ctr[kMtPrefix + 1]) << 32;
     *cut = o.t_desc ? ~key & mt_mask(o.t_width) : key;
   }
-  return map_scan_report(vm, m, o, s, r, keys, values, evict, host, evict ? "map evict" : "map top");
+  return map_scan_report(vm, m, o, s, r, keys, values, evict ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, host, evict ? "map evict" : "map top");
 }
 static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
   MapOpCall c;
@@ -4796,6 +4802,98 @@ int xe_map_scan(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void*
 }
 int xe_map_expire(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries, uint64_t* matched) {
   return map_scan_run(vm, mi, f, keys, values, cap_entries, matched, nullptr, true, true);
+}
+
+// Modify (xe_mapops.h MODIFY_TILE .. MODIFY_KEYED). The edit list checked and copied into the call's descriptor.
+static int map_edits_setup(xe_vm* vm, const HostMap* m, const xe_map_edit* edits, uint32_t n_edits, XeMapOp& o) {
+  if (!edits) return fail(vm, XE_ERR_INVAL, "null map edits");
+  if (!n_edits || n_edits > XE_MM_MAX_EDITS) return fail(vm, XE_ERR_INVAL, "map edit: between 1 and XE_MM_MAX_EDITS edits");
+  for (uint32_t e = 0; e < n_edits; e++) {
+    const xe_map_edit& d = edits[e];
+    if (d.op >= kMmOps) return fail(vm, XE_ERR_INVAL, "map edit: unknown op");
+    if (d.flags & ~XE_MM_OPERAND_FIELD) return fail(vm, XE_ERR_INVAL, "map edit: unknown flag");
+    if (int r = check_field(vm, {"map edit: width", "map edit: the field", "value"}, d.offset, d.width, m->def.value_size)) return r;
+    if ((d.flags & XE_MM_OPERAND_FIELD) && (d.operand > m->def.value_size || d.operand + d.width > m->def.value_size))
+      return fail(vm, XE_ERR_INVAL, "map edit: the operand field lies outside the value");
+    o.m_edits[e] = d;
+  }
+  o.m_n = n_edits;
+  return XE_OK;
+}
+// The walk form. Silent and uncapped (every match is edited, none reported) with a value of up to kMmTileMax
+// bytes: the single pass. Otherwise the scan's SELECT and SCAN, then map_scan_report with the edit behind COPY.
+static int map_modify_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, void* keys,
+                          void* values, uint64_t cap_entries, uint64_t* matched, void* stream, bool host) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, 1, true, host ? nullptr : stream, c);  // (the counters; slots come with r)
+  if (rc < 0) return rc;
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  if (int e = map_edits_setup(vm, m, edits, n_edits, o)) return e;
+  *matched = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return XE_OK;
+  uint32_t total = 0;
+  if (!keys && !values && cap_entries >= m->def.max_entries && o.value_size <= kMmTileMax) {
+    if (int r = mapop_steps(vm, o, {XE_MO_MODIFY_TILE}, s)) return r;
+    if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map modify");
+    *matched = total;
+    if (total) map_written(vm, m);
+    return XE_OK;
+  }
+  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
+  if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map modify");
+  *matched = total;
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), keys, values, XE_MO_MODIFY_EDIT, host,
+                         "map modify");
+}
+int xe_map_modify_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, void* d_keys,
+                         void* d_values, uint64_t cap_entries, uint64_t* matched, void* stream) {
+  return map_modify_run(vm, mi, f, edits, n_edits, d_keys, d_values, cap_entries, matched, stream, false);
+}
+int xe_map_modify(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, void* keys, void* values,
+                  uint64_t cap_entries, uint64_t* matched) {
+  return map_modify_run(vm, mi, f, edits, n_edits, keys, values, cap_entries, matched, nullptr, true);
+}
+// The keyed form: the values from before are complete (the lookup's launches) before MARK names one
+// repetition of each present key and KEYED lets it edit.
+int xe_map_modify_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, const xe_map_edit* edits, uint32_t n_edits,
+                               void* d_values, void* d_found, void* stream) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = mapop_begin(vm, mi, d_keys ? count : 0, true, stream, c);
+  if (rc < 0) return rc;
+  if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
+  if (int e = map_edits_setup(vm, m, edits, n_edits, o)) return e;
+  if (rc == 1) return XE_OK;
+  o.keys = (const uint8_t*)d_keys;
+  o.values_out = (uint8_t*)d_values;
+  o.found = (uint8_t*)d_found;
+  if (int r = array_win(vm, m, o, s)) return r;
+  if (d_values) {
+    if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
+    if (o.value_size > kMoInline)
+      if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s)) return r;
+  } else {
+    if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND}, s)) return r;
+  }
+  if (int r = mapop_steps(vm, o, {XE_MO_MODIFY_MARK, XE_MO_MODIFY_KEYED}, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map modify batch");
+  map_written(vm, m);
+  return XE_OK;
+}
+int xe_map_modify_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, const xe_map_edit* edits, uint32_t n_edits, void* values,
+                        uint8_t* found) {
+  if (!vm) return XE_ERR_INVAL;
+  HostMap* m = get_map(vm, mi);
+  if (!m || !count || !keys || count > kMoMaxCount) return xe_map_modify_batch_device(vm, mi, keys, count, edits, n_edits, values, found, nullptr);
+  if (int rc = stage_in(vm, m, count, keys, nullptr, values != nullptr, found != nullptr)) return rc;
+  if (int rc = xe_map_modify_batch_device(vm, mi, vm->d_mo_keys, count, edits, n_edits, values ? vm->d_mo_vals : nullptr,
+                                          found ? vm->d_mo_found : nullptr, nullptr))
+    return rc;
+  return stage_out(vm, m, count, values, found);
 }
 
 int xe_map_top_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* d_keys, void* d_values, uint64_t k,

@@ -70,6 +70,23 @@ class MapOrder:
     descending: bool = True
 
 
+MM_SET, MM_ADD, MM_SUB, MM_ADD_SAT, MM_SUB_SAT, MM_AND, MM_OR, MM_XOR, MM_MIN, MM_MAX, MM_SHR = range(11)  # XE_MM_*
+MM_OPERAND_FIELD = 1  # XE_MM_OPERAND_FIELD
+MM_MAX_EDITS = 8  # XE_MM_MAX_EDITS
+
+
+@dataclass
+class MapEdit:
+    """xe_map_edit: `op` applied to the unsigned little-endian field of `width` bytes at byte `offset` of the
+    value, with `operand`, or, when `operand_field`, with the field of the same width at byte `operand` of the
+    same value (VM.map_modify / VM.map_modify_batch)."""
+    op: int = MM_SET
+    offset: int = 0
+    width: int = 8
+    operand: int = 0
+    operand_field: bool = False
+
+
 MG_KEY, MG_VALUE, MG_NONE = 0, 1, 0xffffffff  # XE_MG_* (include/xdpemu.h)
 MC_COUNT_ONLY = 1  # XE_MC_COUNT_ONLY
 
@@ -404,6 +421,81 @@ class VM:
     def map_expire(self, m: int, flt: "MapFilter | None" = None, cap: int | None = None, on_device: bool = False):
         """map_scan that also removes the r entries it returns (HASH; xe_map_expire_device)."""
         return self._map_scan(m, flt, cap, on_device, True)
+
+    # ---- in-place edits of value fields on the device copy (xe_map_modify_device / xe_map_modify_batch_device)
+    @staticmethod
+    def _c_edits(edits):
+        edits = list(edits)
+        arr = (N.MapEdit * max(len(edits), 1))()
+        for i, e in enumerate(edits):
+            arr[i] = N.MapEdit(e.op, e.offset, e.width, MM_OPERAND_FIELD if e.operand_field else 0, e.operand)
+        return arr, len(edits)
+
+    def map_modify(self, m: int, edits, flt: "MapFilter | None" = None, cap: int | None = None, on_device: bool = False,
+                   report: bool = True):
+        """(keys[r, key_size], values_before[r, value_size], matched): the `edits` (MapEdit, in list order)
+        applied in place to the first r = min(matched, cap) entries of the device copy that satisfy `flt`, in
+        map_scan's order; the values are those from before the edits. cap None: every match (counted first, then
+        fetched). report False: nothing is reported and only matched is returned. on_device: CUDA tensors."""
+        d = self.map_defs[m]
+        ks = 4 if d.type in ARRAY_TYPES else d.key_size
+        ce, ne = self._c_edits(edits)
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        fp = None if cf is None else C.byref(cf)
+        n = C.c_uint64(0)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.settings.device)
+            # the calls run on the VM's stream: whatever torch has queued on its own completes first
+            torch.cuda.current_stream(dev).synchronize()
+        if not report:
+            room = (1 << 64) - 1 if cap is None else cap
+            self._check(self.lib.map_modify_device(self.h, m, fp, ce, ne, None, None, room, C.byref(n), None), "map modify")
+            return int(n.value)
+        if cap is None:  # count first, then fetch all
+            self._check(self.lib.map_scan_device(self.h, m, fp, None, None, 0, C.byref(n), None), "map modify")
+            cap = n.value
+        if on_device:
+            # (the call writes the r entries it reports; the rest is cut off below)
+            keys = torch.empty((cap, ks), dtype=torch.uint8, device=dev)
+            vals = torch.empty((cap, d.value_size), dtype=torch.uint8, device=dev)
+            rc = self.lib.map_modify_device(self.h, m, fp, ce, ne, keys.data_ptr() or None, vals.data_ptr() or None, cap,
+                                            C.byref(n), None)
+        else:
+            keys = np.zeros((cap, ks), dtype=np.uint8)
+            vals = np.zeros((cap, d.value_size), dtype=np.uint8)
+            rc = self.lib.map_modify(self.h, m, fp, ce, ne, keys.ctypes.data if cap else None, vals.ctypes.data if cap else None,
+                                     cap, C.byref(n))
+        self._check(rc, "map modify")
+        r = min(int(n.value), cap)
+        return keys[:r], vals[:r], int(n.value)
+
+    def map_modify_batch(self, m: int, keys, edits, on_device: bool | None = None):
+        """(values_before[n, value_size], found[n]): the `edits` applied in place to the entries of n keys on
+        the device copy, once per distinct present key; absent keys are reported and nothing is created.
+        on_device None: CUDA tensors for keys give tensors back (xe_map_modify_batch_device), numpy arrays go
+        through staging; True / False: the keys are moved to the device / the host first."""
+        d = self.map_defs[m]
+        if on_device is not None and on_device != self._is_dev(keys):
+            if on_device:
+                import torch
+                keys = torch.from_numpy(np.ascontiguousarray(keys).view(np.uint8)).to(torch.device("cuda", self.settings.device))
+            else:
+                keys = keys.cpu().numpy()
+        k, n = self._mo_keys(m, keys)
+        ce, ne = self._c_edits(edits)
+        if self._is_dev(k):
+            import torch
+            vals = torch.empty((n, d.value_size), dtype=torch.uint8, device=k.device)
+            found = torch.empty(n, dtype=torch.uint8, device=k.device)
+            rc = self.lib.map_modify_batch_device(self.h, m, k.data_ptr() or None, n, ce, ne, vals.data_ptr() or None,
+                                                  found.data_ptr() or None, None)
+        else:
+            vals = np.zeros((n, d.value_size), dtype=np.uint8)
+            found = np.zeros(n, dtype=np.uint8)
+            rc = self.lib.map_modify_batch(self.h, m, k.ctypes.data, n, ce, ne, vals.ctypes.data, found.ctypes.data)
+        self._check(rc, "map modify batch")
+        return vals, found
 
     # ---- top-K, evict and statistics on the device copy (xe_map_top_device / xe_map_evict_device / xe_map_stats)
     def _map_top(self, m: int, order: "MapOrder", k: int, flt, on_device: bool, ranked: bool, evict: bool):

@@ -440,6 +440,76 @@ int xe_map_scan(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* keys, 
 int xe_map_expire(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
                   uint64_t* matched);
 
+/* --- in-place edits of value fields on the device copy (ARRAY and HASH kinds): read-and-reset of counters,
+ * token-bucket refills, decay and ageing, for the entries a filter selects (the walk form) or for a batch of
+ * keys (the keyed form), by kernels that change the fields where they lie. Nothing of the map crosses to the
+ * host or back and no key is probed for again. The rules of the batched calls above hold: pipelined batches
+ * complete first (xe_sync), a map changed through the host calls is uploaded once, the call is finished when
+ * it returns, stream NULL is the VM's stream, every d_* is a device address (a host address in the
+ * host-simulation build); LRU_HASH, QUEUE, STACK and PERF_EVENT_ARRAY maps return XE_ERR_UNSUPPORTED; the
+ * calls are refused with XE_ERR_INVAL while a shard epoch is open. `edits` is host memory in every form.
+ *
+ *   edits:   n_edits (1 .. XE_MM_MAX_EDITS) edits, applied in list order to the value as it stands: fields may
+ *            overlap and a later edit sees the earlier ones. A field is `width` bytes (1, 2, 4 or 8) at byte
+ *            `offset` of the value, any alignment, little endian, unsigned. The operand is a u64: SET, ADD,
+ *            SUB, AND, OR and XOR take it mod 2^(8*width); for ADD_SAT, SUB_SAT, MIN and MAX an operand larger
+ *            than the field can hold acts as 2^(8*width) - 1; SHR by 8*width or more gives 0. Under
+ *            XE_MM_OPERAND_FIELD `operand` is instead the byte offset in the same value of a field of the same
+ *            width that holds the operand; it is read when its edit runs, so after the earlier edits.
+ *   filter:  the scan's, evaluated once per entry on the value from before the first edit.
+ *   nil:     a HASH value whose backing became nil reads as zeros for the filter, in the reported value and as
+ *            the start of the edits; a selected one is an ordinary value afterwards (zeros plus the edits).
+ *   state:   the entry count, the slot layout, every record's key words, the tombstones and every entry that
+ *            is not selected stay byte for byte. The result is that of xe_map_update_batch_device given the
+ *            same keys with the edited values: the whole value of each modified entry is also written to the
+ *            delta base of xe_map_delta (a control-plane write never shows up as packet adds; adds still
+ *            pending on that entry are dropped, as an update drops them); no other entry's base is touched.
+ *   walk:    xe_map_modify_device. The entries, the filter and the order are xe_map_scan_device's (ARRAY:
+ *            every index below max_entries). *matched = the number of matching entries, always the total.
+ *            Exactly the r = min(*matched, cap_entries) first matches in slot order are modified; their keys
+ *            and their values from before the modification go to d_keys / d_values (either may be NULL; no
+ *            byte past entry r is written). With both NULL up to cap_entries matches are modified silently;
+ *            cap_entries 0 only counts.
+ *   keyed:   xe_map_modify_batch_device. d_found[i] = key i is present (may be NULL); d_values (may be NULL)
+ *            gets value i from before the call, zero-filled when absent; both are the same for every
+ *            repetition of a key. Each distinct present key is edited exactly once, however often the batch
+ *            repeats it. Absent keys and ARRAY indices >= max_entries are reported absent; nothing is created.
+ *   errors:  XE_ERR_INVAL with nothing changed: edits NULL, n_edits 0 or above XE_MM_MAX_EDITS, an unknown op
+ *            or flag bit, another width, a field or an operand field that does not lie inside value_size, the
+ *            filter's errors, matched NULL (walk), keys NULL with count > 0, count above 2^31.
+ *   not served: per-key operands, signed ops, edits of key bytes, LRU maps. */
+#define XE_MM_SET 0       /* field = operand */
+#define XE_MM_ADD 1       /* (field + operand) mod 2^(8*width) */
+#define XE_MM_SUB 2       /* (field - operand) mod 2^(8*width) */
+#define XE_MM_ADD_SAT 3   /* min(field + operand, 2^(8*width) - 1) */
+#define XE_MM_SUB_SAT 4   /* field > operand ? field - operand : 0 */
+#define XE_MM_AND 5
+#define XE_MM_OR 6
+#define XE_MM_XOR 7
+#define XE_MM_MIN 8       /* unsigned */
+#define XE_MM_MAX 9
+#define XE_MM_SHR 10      /* field >> operand; a shift of 8*width or more gives 0 */
+#define XE_MM_OPERAND_FIELD 1u  /* flags: the operand is read from the entry's own value (above) */
+#define XE_MM_MAX_EDITS 8
+typedef struct xe_map_edit {
+  uint32_t op;      /* XE_MM_* */
+  uint32_t offset;  /* byte offset of the field inside the value; any alignment */
+  uint32_t width;   /* 1, 2, 4 or 8 bytes, little endian, unsigned */
+  uint32_t flags;   /* 0 or XE_MM_OPERAND_FIELD */
+  uint64_t operand; /* the operand; under XE_MM_OPERAND_FIELD the byte offset in the value of a field of
+                       the same width that holds it */
+} xe_map_edit;
+int xe_map_modify_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits,
+                         void* d_keys, void* d_values, uint64_t cap_entries, uint64_t* matched, void* stream);
+int xe_map_modify_batch_device(xe_vm* vm, int32_t map_idx, const void* d_keys, uint64_t count, const xe_map_edit* edits,
+                               uint32_t n_edits, void* d_values, void* d_found, void* stream);
+/* The same with host pointers: the reported entries (walk) or the keys and the outputs (keyed) are staged
+ * through device buffers of the VM. */
+int xe_map_modify(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits,
+                  void* keys, void* values, uint64_t cap_entries, uint64_t* matched);
+int xe_map_modify_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t count, const xe_map_edit* edits,
+                        uint32_t n_edits, void* values, uint8_t* found);
+
 /* --- top-K, evict and value statistics on the device copy (ARRAY and HASH kinds): the k entries that rank
  * first by one field of the value, their removal, and the count, sum, minimum and maximum of a field, by
  * kernels that read the slot table at device bandwidth; only the selected entries leave the device. The
