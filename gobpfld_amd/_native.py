@@ -86,6 +86,11 @@ class MapGroup(C.Structure):  # xe_map_group_spec
                 ("measure_width", C.c_uint32), ("count_off", C.c_uint32), ("sum_off", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class MapJoin(C.Structure):  # xe_map_join_spec
+    _fields_ = [("from_", C.c_uint32), ("offset", C.c_uint32), ("len", C.c_uint32), ("mode", C.c_uint32),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class MapEdit(C.Structure):  # xe_map_edit
     _fields_ = [("op", C.c_uint32), ("offset", C.c_uint32), ("width", C.c_uint32), ("flags", C.c_uint32),
                 ("operand", C.c_uint64)]
@@ -189,6 +194,8 @@ _SIGS = {
     "map_evict": (C.c_int, [P, C.c_int32, P, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "map_stats": (C.c_int, [P, C.c_int32, P, P, P, P]),
     "map_group": (C.c_int, [P, C.c_int32, P, P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), P]),
+    "map_join_device": (C.c_int, [P, C.c_int32, P, P, C.c_int32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), P]),
+    "map_join": (C.c_int, [P, C.c_int32, P, P, C.c_int32, P, P, P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "map_compact": (C.c_int, [P, C.c_int32, C.c_uint32, P, P]),
     "map_modify_device": (C.c_int, [P, C.c_int32, P, P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
     "map_modify": (C.c_int, [P, C.c_int32, P, P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -228,7 +235,7 @@ HEADER_SYMBOLS = [
     "xe_map_lookup_batch", "xe_map_update_batch_staged", "xe_map_delete_batch", "xe_debug_map_traffic",
     "xe_map_scan_device", "xe_map_expire_device", "xe_map_scan", "xe_map_expire",
     "xe_map_top_device", "xe_map_evict_device", "xe_map_top", "xe_map_evict", "xe_map_stats",
-    "xe_map_group", "xe_map_compact",
+    "xe_map_group", "xe_map_join_device", "xe_map_join", "xe_map_compact",
     "xe_map_modify_device", "xe_map_modify", "xe_map_modify_batch_device", "xe_map_modify_batch",
     "xe_set_kernel_cache", "xe_kernel_source", "xe_compile_kernel_source", "xe_kernel_object_name",
     "xe_kernel_cache_stats",

@@ -1,7 +1,7 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
 // xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device,
 // xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group, xe_map_compact, xe_map_modify_device,
-// xe_map_modify_batch_device): the per-key and per-slot decision logic that the kernels
+// xe_map_modify_batch_device, xe_map_join_device): the per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
 // declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
 //
@@ -113,6 +113,20 @@
 //                    one of a key's repetitions is named, decided before any value byte moves
 //            KEYED   a sub-group per entry; the one whose i + 1 is still there edits the slot as EDIT does and
 //                    clears the word: each distinct present key is edited exactly once
+//   join     SELECT  (JOIN_SELECT, in place of the scan's) the SELECT shape over the source's slots: a lane evaluates
+//                    the filter on its slot, the four rounds' loads in flight together; a candidate then assembles
+//                    its join key (the group's rule: some bytes of its key or value) and probes the other map
+//                    read-only (an ARRAY: the index against max_entries). The bit that goes to the bitmap and the
+//                    tile counts is "kept": present under mode 0, absent under mode 1. The probes diverge, the
+//                    ballots stand behind them where the wave is whole again. The candidates are counted once per
+//                    wave (kMjSelected). Nothing per entry is written: one bit
+//            SCAN, SCATTER, COPY   (the scan's: matched, slot[j], the kept entries' keys and values)
+//            VALUE   (JOIN_VALUE, when the other map's values are wanted) a sub-group per reported entry j < r, as
+//                    wide as the OTHER map's value asks: the join key is rebuilt from slot[j] and probed again (no
+//                    per-entry scratch beyond slot), the value found (zeros when nil-backed, and always under mode
+//                    1) goes to entry j of the third output. Behind COPY and in front of EXPIRE: a join of a map
+//                    with itself reads everything before anything is removed
+//            EXPIRE  (the scan's, under XE_MJ_REMOVE)
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
 // an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
@@ -141,6 +155,7 @@ enum : uint32_t {
   XE_MO_GROUP_LOCATE, XE_MO_GROUP_UNDO, XE_MO_GROUP_PUBLISH, XE_MO_GROUP_ADD,
   XE_MO_COMPACT_MARK, XE_MO_COMPACT_REBUILD,
   XE_MO_MODIFY_TILE, XE_MO_MODIFY_EDIT, XE_MO_MODIFY_MARK, XE_MO_MODIFY_KEYED,
+  XE_MO_JOIN_SELECT, XE_MO_JOIN_VALUE,
   XE_MO_STEPS
 };
 
@@ -173,6 +188,8 @@ constexpr uint32_t kMcFree = 4, kMcMoved = 5, kMcLongest = 6, kMcLong = 7, kMcMa
 // bytes on their slot's lane (MODIFY_TILE), larger ones go the general way where a sub-group shares a value
 enum : uint32_t { kMmSet = 0, kMmAdd, kMmSub, kMmAddSat, kMmSubSat, kMmAnd, kMmOr, kMmXor, kMmMin, kMmMax, kMmShr, kMmOps };
 constexpr uint32_t kMmTileMax = 64;
+// join: the candidates (the entries the filter selects, kept or not), a counter word
+constexpr uint32_t kMjSelected = 4;
 static_assert(kMmTileMax >= kMoInline, "the single pass serves at least the values that move on one lane");
 // the filter's ops (include/xdpemu.h XE_MF_*)
 enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
@@ -208,13 +225,16 @@ struct XeMapOp : XeMapView {
   uint32_t* bins;         // [kMtBins] zero between the passes
   uint64_t* bitmap2;      // [tiles x kMsRounds] key == cut
   uint32_t* tile2;        // [tiles] equals per tile (CUT), then the equals in front of the tile (SCAN)
-  // group: the destination map beside the source above
+  // group: the destination map beside the source above; join: the other map, only read
   XeMapView dst;
-  uint32_t g_from, g_off, g_len;     // the group bytes: 0 the source key / 1 the source value, first byte, number
+  uint32_t g_from, g_off, g_len;     // the group / join bytes: 0 the source key / 1 the source value, first byte, number
   uint32_t g_moff, g_mwidth;         // the measure in the source value (width 0: none)
   uint32_t g_count_off, g_sum_off;   // the accumulators in the destination value (kMgNone: none)
   // compact
   uint32_t c_only;        // 1: REBUILD measures and changes nothing
+  // join
+  uint32_t j_mode;        // 0: the entries whose join key is an entry of dst are kept; 1: those whose key is not
+  uint8_t* j_values;      // n x dst.value_size: the joined entries' values (JOIN_VALUE)
   // modify
   uint32_t m_n;           // the edits in use
   xe_map_edit m_edits[XE_MM_MAX_EDITS];  // checked by the runtime: op, width, the field and an operand field inside the value
@@ -940,6 +960,25 @@ XE_HD void mm_keyed_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint32_t la
   mm_modify_item(o, s, sub, lanes, true);
 }
 
+// ---------------------------------------------------------------- join
+// JOIN_SELECT: is the candidate in source slot sbase + s (ms_select_item said yes) kept? Its join key is the
+// group's (mg_group_key), the probe of the other map read-only (find: as mo_slot_of's): a FULL record that
+// holds the key, nil-backed or not, is present, a tombstone is not; an ARRAY index at or beyond max_entries is absent.
+template <class Find>
+XE_HD bool mj_kept_item(const XeMapOp& o, uint32_t s, Find find) {
+  return (mg_slot_of(o, s, find) != kMoAbsent) != (o.j_mode != 0);
+}
+// JOIN_VALUE, reported entry j by lane `sub` of the `lanes` that share it: the value of the entry that slot[j]
+// joined with, found again from slot[j] alone; zeros when it is nil-backed, and always under mode 1 (no probe).
+template <class Find>
+XE_HD void mj_value_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t lanes, Find find) {
+  const uint32_t ds = o.j_mode ? kMoAbsent : mg_slot_of(o, o.slot[j] - o.sbase, find);
+  const bool zero = ds == kMoAbsent ||
+                    (o.dst.kind == XE_DM_HASH && (uint32_t(o.dst.recs[uint64_t(ds) * o.dst.rwords]) & XE_SLOT_VLEN0));
+  mo_move(o.j_values + uint64_t(j) * o.dst.value_size, zero ? nullptr : o.dst.vals + uint64_t(ds) * o.dst.value_size,
+          o.dst.value_size, sub, lanes);
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
 #else
@@ -980,6 +1019,15 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
   using Words = const uint64_t*;
   if (step == XE_MO_SCAN_SELECT) {
     sim_tile_words(tiles, slots([&](uint32_t s) { return ms_select_item(o, s); }),
+                   [&](uint32_t t, Words w1, Words, uint32_t c1, uint32_t) { put(t, w1, nullptr, c1); });
+    return 0;
+  }
+  if (step == XE_MO_JOIN_SELECT) {  // the candidates go to the counters, the kept ones to the bitmap
+    sim_tile_words(tiles, slots([&](uint32_t s) {
+                     if (!ms_select_item(o, s)) return false;
+                     o.ctr[kMjSelected]++;
+                     return mj_kept_item(o, s, mo_find);
+                   }),
                    [&](uint32_t t, Words w1, Words, uint32_t c1, uint32_t) { put(t, w1, nullptr, c1); });
     return 0;
   }
@@ -1121,6 +1169,7 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
       case XE_MO_MODIFY_EDIT: mm_modify_item(o, o.slot[i], 0, 1, false); break;
       case XE_MO_MODIFY_MARK: mm_mark_item(o, i); break;
       case XE_MO_MODIFY_KEYED: mm_keyed_item(o, i, 0, 1); break;
+      case XE_MO_JOIN_VALUE: mj_value_item(o, i, 0, 1, mo_find); break;
       default: return -1;
     }
   }

@@ -1,4 +1,4 @@
-// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group, compact, modify (xe_mapops.h:
+// Device-resident batched map lookup, update and delete, scan / expire, top / evict / stats, group, compact, modify, join (xe_mapops.h:
 // the steps and what each one decides). One kernel per step; a step works either one batch entry per lane
 // (probes, claims, marks) or one entry per sub-group of lanes (value moves, 16 bytes per lane and access where source and
 // destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
@@ -515,12 +515,54 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapmodify_tile_kernel(XeMapOp o
   if ((threadIdx.x & 63) == 0 && cnt) mo_add32(o.ctr + kMoMatched, cnt);
 }
 
+// ---- join. JOIN_SELECT is SELECT with a probe behind the filter: the filter of the four rounds first (their
+// loads are in flight together), then a candidate's lane builds its join key and probes the other table, one
+// round after another (a probe is a dependent chain of loads: what overlaps it is the other waves of the CU).
+// The probes diverge, lane by lane and in the number of groups they read; the ballots stand in a loop of their
+// own behind them, where every lane of the wave arrives (the tile loop's bound is the same for the whole wave),
+// and a lane whose slot lies past the table or is no candidate votes "not kept". The wave's candidates are
+// counted once, after its last tile.
+__global__ void __launch_bounds__(kMoThreads) xe_mapjoin_select_kernel(XeMapOp o, uint32_t tiles) {
+  uint32_t cands = 0;
+  tile_walk(tiles, [&](uint32_t t, uint32_t lane) {
+    uint32_t hit = 0, kept = 0;  // bit r: the slot of round r is a candidate / is kept
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const uint32_t s = tile_slot(t, r, lane);
+      hit |= uint32_t(s < o.nslots && ms_select_item(o, s)) << r;
+    }
+#pragma unroll 1  // (one copy of the probe's code)
+    for (uint32_t r = 0; r < kMsRounds; r++)
+      if (((hit >> r) & 1) && mj_kept_item(o, tile_slot(t, r, lane), find_slot)) kept |= 1u << r;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kMsRounds; r++) {
+      const unsigned long long b = __ballot((kept >> r) & 1);
+      cands += uint32_t(__popcll(__ballot((hit >> r) & 1)));
+      if (lane == 0) o.bitmap[uint64_t(t) * kMsRounds + r] = b;
+      cnt += uint32_t(__popcll(b));
+    }
+    if (lane == 0) o.tile[t] = cnt;
+  });
+  if ((threadIdx.x & 63) == 0 && cands) mo_add32(o.ctr + kMjSelected, cands);
+}
+
+// JOIN_VALUE: one reported entry per LANES consecutive lanes, LANES by the OTHER map's value size. Every lane of
+// a sub-group probes for the same key (the same addresses: one request) and moves its share of the value.
+template <uint32_t LANES>
+__global__ void __launch_bounds__(kMoThreads) xe_mapjoin_value_kernel(XeMapOp o, uint32_t) {
+  const uint32_t sub = threadIdx.x % LANES, per = kMoThreads / LANES;
+  const uint64_t stride = uint64_t(gridDim.x) * per;
+  for (uint64_t j = uint64_t(blockIdx.x) * per + threadIdx.x / LANES; j < o.n; j += stride)
+    mj_value_item(o, uint32_t(j), sub, LANES, find_slot);
+}
+
 // The steps: how each is launched, and its kernel. kLane / kValue: one batch entry per lane / per sub-group of
 // xe_mo_lanes lanes (the kernel's second argument is the step; a value step's kernel is the instantiation for
-// those lanes). kTileSrc / kTileDst: a wave per tile of the source's slots (the second argument is their
-// number) / of the group's destination table, a HASH one (the step). kOneGroup: one workgroup, once the source
-// has a tile.
-enum MoShape : uint32_t { kNoShape = 0, kLane, kValue, kTileSrc, kTileDst, kOneGroup };
+// those lanes; kValueDst: the join's value kernel, the lanes by the other map's value size). kTileSrc /
+// kTileDst: a wave per tile of the source's slots (the second argument is their number) / of the group's
+// destination table, a HASH one (the step). kOneGroup: one workgroup, once the source has a tile.
+enum MoShape : uint32_t { kNoShape = 0, kLane, kValue, kValueDst, kTileSrc, kTileDst, kOneGroup };
 using MoKernel = void (*)(XeMapOp, uint32_t);
 struct MoStep {
   MoShape shape;
@@ -551,12 +593,14 @@ constexpr MoTable mo_table() {
   t.row[XE_MO_COMPACT_MARK] = {kTileSrc, xe_mapcompact_mark_kernel};
   t.row[XE_MO_COMPACT_REBUILD] = {kTileSrc, xe_mapcompact_rebuild_kernel};
   t.row[XE_MO_MODIFY_TILE] = {kTileSrc, xe_mapmodify_tile_kernel};
+  t.row[XE_MO_JOIN_SELECT] = {kTileSrc, xe_mapjoin_select_kernel};
+  t.row[XE_MO_JOIN_VALUE] = {kValueDst, nullptr};
   return t;
 }
 constexpr MoTable kMoSteps = mo_table();
 constexpr bool mo_steps_filled() {
   for (const MoStep& r : kMoSteps.row)
-    if (r.shape == kNoShape || (r.kernel == nullptr) != (r.shape == kValue)) return false;
+    if (r.shape == kNoShape || (r.kernel == nullptr) != (r.shape == kValue || r.shape == kValueDst)) return false;
   return true;
 }
 static_assert(sizeof kMoSteps.row / sizeof kMoSteps.row[0] == XE_MO_STEPS && mo_steps_filled(), "one filled row per step");
@@ -574,12 +618,15 @@ extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream) {
   const MoShape shape = kMoSteps.row[step].shape;
   MoKernel kernel = kMoSteps.row[step].kernel;
   uint32_t blocks = 1, arg = step;
-  if (shape == kLane || shape == kValue) {
+  if (shape == kLane || shape == kValue || shape == kValueDst) {
     if (!op->n) return 0;
-    const uint32_t lanes = shape == kValue ? xe_mo_lanes(op->value_size) : 1, per = kMoThreads / lanes;
+    const uint32_t lanes = shape == kValue ? xe_mo_lanes(op->value_size) : shape == kValueDst ? xe_mo_lanes(op->dst.value_size) : 1;
+    const uint32_t per = kMoThreads / lanes;
     blocks = mo_blocks((uint64_t(op->n) + per - 1) / per);
     if (shape == kValue)
       kernel = lanes == 1 ? xe_mapop_value_kernel<1> : lanes == 4 ? xe_mapop_value_kernel<4> : lanes == 16 ? xe_mapop_value_kernel<16> : xe_mapop_value_kernel<64>;
+    if (shape == kValueDst)
+      kernel = lanes == 1 ? xe_mapjoin_value_kernel<1> : lanes == 4 ? xe_mapjoin_value_kernel<4> : lanes == 16 ? xe_mapjoin_value_kernel<16> : xe_mapjoin_value_kernel<64>;
   } else {
     if (shape == kTileDst && op->dst.kind != XE_DM_HASH) return 0;
     const uint32_t tiles = xe_ms_tiles(shape == kTileDst ? op->dst.cap : op->nslots);

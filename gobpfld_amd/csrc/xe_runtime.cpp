@@ -974,6 +974,7 @@ struct xe_vm {
   void* d_mo_keys = nullptr; size_t d_mo_keys_cap = 0;
   void* d_mo_vals = nullptr; size_t d_mo_vals_cap = 0;
   void* d_mo_found = nullptr; size_t d_mo_found_cap = 0;
+  void* d_mo_join = nullptr; size_t d_mo_join_cap = 0;  // staging of xe_map_join's third output
   void* d_ms = nullptr; size_t d_ms_cap = 0;  // scan / expire: the table's bitmap and the tile counts
 };
 // ---- keyed ordered execution buffers (XeKeyed), sized for n packets
@@ -1720,7 +1721,7 @@ void xe_destroy(xe_vm* vm) {
   dev_free(vm->d_arena_par); dev_free(vm->d_arena_seq); dev_free(vm->d_ksnap);
   dev_free(vm->d_umem); dev_free(vm->d_desc); dev_free(vm->d_res); dev_free(vm->d_ver); dev_free(vm->d_regs);
   dev_free(vm->d_usnap); dev_free(vm->d_ovl); dev_free(vm->d_app); dev_free(vm->d_app_sort); dev_free(vm->d_relink);
-  dev_free(vm->d_mo); dev_free(vm->d_mo_keys); dev_free(vm->d_mo_vals); dev_free(vm->d_mo_found); dev_free(vm->d_ms);
+  dev_free(vm->d_mo); dev_free(vm->d_mo_keys); dev_free(vm->d_mo_vals); dev_free(vm->d_mo_found); dev_free(vm->d_mo_join); dev_free(vm->d_ms);
   keyed_free(vm);
   vm->t0.fini(); vm->t1.fini(); vm->t2.fini();
 #ifndef XE_HOSTSIM
@@ -4549,23 +4550,28 @@ static int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp
 }
 // The r entries the bitmap and the tile bases select: SCATTER, COPY, the step `after` on the same entries
 // (XE_MO_SCAN_EXPIRE removes them, XE_MO_MODIFY_EDIT edits them, XE_MO_STEPS: none), the staging back to the
-// host, the synchronisation and the host's view of a map that lost entries or was written.
+// host, the synchronisation and the host's view of a map that lost entries or was written. joined (the join's
+// third output, r x o.dst.value_size): JOIN_VALUE behind COPY, in front of `after`.
 static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uint32_t r, void* keys, void* values, uint32_t after,
-                           bool host, const char* what) {
+                           bool host, const char* what, void* joined = nullptr) {
   const bool out = keys || values, remove = after == XE_MO_SCAN_EXPIRE, modify = after == XE_MO_MODIFY_EDIT;
-  if (!r || (!remove && !modify && !out)) return XE_OK;
-  const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size;
+  if (!r || (!remove && !modify && !out && !joined)) return XE_OK;
+  const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size, jb = joined ? size_t(r) * o.dst.value_size : 0;
   if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
   o.ctr = (uint32_t*)vm->d_mo;
   o.slot = o.ctr + kMoCounters;
   o.n = r;
-  if (host && ((keys && ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb)) || (values && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb))))
+  if (host && ((keys && ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb)) || (values && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb)) ||
+               (joined && ensure_buf(&vm->d_mo_join, &vm->d_mo_join_cap, jb))))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
   o.keys_out = (uint8_t*)(!keys ? nullptr : host ? vm->d_mo_keys : keys);
   o.values_out = (uint8_t*)(!values ? nullptr : host ? vm->d_mo_vals : values);
+  o.j_values = (uint8_t*)(!joined ? nullptr : host ? vm->d_mo_join : joined);
   if (int e = mapop_steps(vm, o, {XE_MO_SCAN_SCATTER}, s)) return e;
   if (out)
     if (int e = mapop_steps(vm, o, {XE_MO_SCAN_COPY}, s)) return e;
+  if (joined && jb)
+    if (int e = mapop_steps(vm, o, {XE_MO_JOIN_VALUE}, s)) return e;
   uint32_t cnt = 0;
   if (remove) {
     if (int e = mapop_steps(vm, o, {XE_MO_SCAN_EXPIRE}, s)) return e;
@@ -4573,7 +4579,8 @@ static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uin
   }
   if (modify)
     if (int e = mapop_steps(vm, o, {XE_MO_MODIFY_EDIT}, s)) return e;
-  if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s))))
+  if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s)) ||
+               (jb && d2h(joined, vm->d_mo_join, jb, s))))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
   if (remove) m->live = cnt;
@@ -4746,6 +4753,70 @@ static int map_group_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const x
 int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst_map, uint64_t* matched,
                  uint64_t* created, void* stream) {
   return map_group_run(vm, src_map, f, g, dst_map, matched, created, stream);
+}
+
+// Join (xe_mapops.h JOIN_SELECT in place of the scan's SELECT, then SCAN and map_scan_report with JOIN_VALUE): the
+// scan's run with a second map that is only read. Only the source is written, and only on removal.
+static int map_join_check(xe_vm* vm, const HostMap* sm, const HostMap* om, const xe_map_join_spec* j) {
+  if (j->from > XE_MG_VALUE) return fail(vm, XE_ERR_INVAL, "map join: from must be XE_MG_KEY or XE_MG_VALUE");
+  if (j->mode > XE_MJ_ABSENT) return fail(vm, XE_ERR_INVAL, "map join: mode must be XE_MJ_PRESENT or XE_MJ_ABSENT");
+  if (j->flags & ~XE_MJ_REMOVE) return fail(vm, XE_ERR_INVAL, "map join: unknown flag");
+  if (j->pad) return fail(vm, XE_ERR_INVAL, "map join: pad must be 0");
+  const uint32_t src_key = sm->dkind == XE_DM_ARRAY ? 4 : sm->def.key_size;
+  if (uint64_t(j->offset) + j->len > (j->from == XE_MG_KEY ? src_key : sm->def.value_size))
+    return fail(vm, XE_ERR_INVAL, "map join: the join bytes lie outside the source key / value");
+  if (om->dkind == XE_DM_HASH) {
+    if (!om->def.key_size) return fail(vm, XE_ERR_INVAL, "map join: the other map has no key bytes");
+    if (j->len != om->def.key_size) return fail(vm, XE_ERR_INVAL, "map join: len must be the other map's key_size");
+  } else if (j->len != 1 && j->len != 2 && j->len != 4) {
+    return fail(vm, XE_ERR_INVAL, "map join: len must be 1, 2 or 4 for an ARRAY other map");
+  }
+  if ((j->flags & XE_MJ_REMOVE) && sm->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
+  return XE_OK;
+}
+static int map_join_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other, void* keys,
+                        void* values, void* joined, uint64_t cap_entries, uint64_t* matched, uint64_t* selected, void* stream,
+                        bool host) {
+  if (!vm) return XE_ERR_INVAL;
+  if (int rc = xe_sync(vm)) return rc;
+  const bool remove = j && (j->flags & XE_MJ_REMOVE);
+  HostMap *sm = nullptr, *om = nullptr;
+  if (int rc = mapop_map(vm, src, remove, &sm)) return rc;
+  if (int rc = mapop_map(vm, other, false, &om)) return rc;
+  if (!j) return fail(vm, XE_ERR_INVAL, "null map join spec");
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (int rc = map_join_check(vm, sm, om, j)) return rc;
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  if (int rc = mapop_begin(vm, src, 1, remove, host ? nullptr : stream, c)) return rc;  // (the counters; slots come with r)
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  if (int rc = mapop_current(vm, om)) return rc;
+  *matched = 0;
+  if (selected) *selected = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return XE_OK;
+  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  o.dst = map_view(*om);
+  o.g_from = j->from;
+  o.g_off = j->offset;
+  o.g_len = j->len;
+  o.j_mode = j->mode;
+  if (int r = mapop_steps(vm, o, {XE_MO_JOIN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
+  uint32_t ctr[kMoCounters];
+  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map join");
+  *matched = ctr[kMoMatched];
+  if (selected) *selected = ctr[kMjSelected];
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(ctr[kMoMatched], cap_entries)), keys, values,
+                         remove ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, host, "map join", joined);
+}
+int xe_map_join_device(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other_map, void* d_keys,
+                       void* d_values, void* d_other_values, uint64_t cap_entries, uint64_t* matched, uint64_t* selected,
+                       void* stream) {
+  return map_join_run(vm, src_map, f, j, other_map, d_keys, d_values, d_other_values, cap_entries, matched, selected, stream, false);
+}
+int xe_map_join(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other_map, void* keys,
+                void* values, void* other_values, uint64_t cap_entries, uint64_t* matched, uint64_t* selected) {
+  return map_join_run(vm, src_map, f, j, other_map, keys, values, other_values, cap_entries, matched, selected, nullptr, true);
 }
 
 // Compact (xe_mapops.h MARK, SCAN, REBUILD): the counters are read after SCAN (no tombstone: nothing is

@@ -106,6 +106,21 @@ class MapGroup:
     measure_width: int = 0
 
 
+MJ_PRESENT, MJ_ABSENT = 0, 1  # XE_MJ_* modes (include/xdpemu.h)
+MJ_REMOVE = 1  # XE_MJ_REMOVE
+
+
+@dataclass
+class MapJoin:
+    """xe_map_join_spec: the join key is the `len` bytes at byte `offset` of the source entry's key (`from_` MG_KEY;
+    an ARRAY source's index as a u32) or value (MG_VALUE); `mode` MJ_PRESENT keeps the entries whose join key is an
+    entry of the other map, MJ_ABSENT those whose key is not (VM.map_join)."""
+    from_: int = MG_KEY
+    offset: int = 0
+    len: int = 4
+    mode: int = MJ_PRESENT
+
+
 @dataclass
 class Settings:
     max_steps: int = 1 << 20
@@ -571,6 +586,49 @@ class VM:
         self._check(self.lib.map_group(self.h, src, None if cf is None else C.byref(cf), C.byref(cg), dst, C.byref(n),
                                        C.byref(new), None), "map group")
         return int(n.value), int(new.value)
+
+    def map_join(self, src: int, other: int, join: "MapJoin", flt: "MapFilter | None" = None, cap: int | None = None,
+                 on_device: bool = False, remove: bool = False, other_values: bool = False):
+        """(keys[r], values[r][, other_values[r]], matched, selected): the entries of map `src` that `flt` selects
+        (selected of them) and whose join key is (MJ_PRESENT) or is not (MJ_ABSENT) an entry of map `other`
+        (matched of them), in map_scan's order; r = min(matched, cap). cap None: count first, then fetch them
+        all. other_values: also the values of the entries of `other` they joined with (zeros under MJ_ABSENT).
+        remove: the r returned entries are removed from `src` (HASH). on_device: CUDA tensors (xe_map_join_device)."""
+        d, od = self.map_defs[src], self.map_defs[other]
+        ks = 4 if d.type in ARRAY_TYPES else d.key_size
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        fp = None if cf is None else C.byref(cf)
+        cj0 = N.MapJoin(join.from_, join.offset, join.len, join.mode, 0, 0)  # (counting removes nothing)
+        cj = N.MapJoin(join.from_, join.offset, join.len, join.mode, MJ_REMOVE if remove else 0, 0)
+        n, sel = C.c_uint64(0), C.c_uint64(0)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.settings.device)
+            # the calls run on the VM's stream: whatever torch has queued on its own completes first
+            torch.cuda.current_stream(dev).synchronize()
+        if cap is None:  # count first, then fetch all
+            self._check(self.lib.map_join_device(self.h, src, fp, C.byref(cj0), other, None, None, None, 0, C.byref(n),
+                                                 C.byref(sel), None), "map join")
+            cap = n.value
+        if on_device:
+            # (the call writes the r entries it reports; the rest is cut off below)
+            keys = torch.empty((cap, ks), dtype=torch.uint8, device=dev)
+            vals = torch.empty((cap, d.value_size), dtype=torch.uint8, device=dev)
+            ovals = torch.empty((cap, od.value_size), dtype=torch.uint8, device=dev) if other_values else None
+            rc = self.lib.map_join_device(self.h, src, fp, C.byref(cj), other, keys.data_ptr() or None, vals.data_ptr() or None,
+                                          (ovals.data_ptr() or None) if other_values else None, cap, C.byref(n), C.byref(sel), None)
+        else:
+            keys = np.zeros((cap, ks), dtype=np.uint8)
+            vals = np.zeros((cap, d.value_size), dtype=np.uint8)
+            ovals = np.zeros((cap, od.value_size), dtype=np.uint8) if other_values else None
+            rc = self.lib.map_join(self.h, src, fp, C.byref(cj), other, keys.ctypes.data if cap else None,
+                                   vals.ctypes.data if cap else None, ovals.ctypes.data if other_values and cap else None, cap,
+                                   C.byref(n), C.byref(sel))
+        self._check(rc, "map join")
+        r = min(int(n.value), cap)
+        if other_values:
+            return keys[:r], vals[:r], ovals[:r], int(n.value), int(sel.value)
+        return keys[:r], vals[:r], int(n.value), int(sel.value)
 
     def map_compact(self, m: int, count_only: bool = False) -> dict:
         """{tombstones, moved, longest_run, via_host}: every tombstone of HASH map `m` removed on the device

@@ -603,6 +603,61 @@ typedef struct xe_map_group_spec {
 int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst_map,
                  uint64_t* matched, uint64_t* created, void* stream);
 
+/* --- join on the device copy (ARRAY and HASH kinds, either side): the entries of one map that satisfy a filter
+ * and whose join key, some bytes of their key or value, IS (a semi-join) or is NOT (an anti-join) an entry of
+ * another map of the same VM; optionally the values of the entries they joined with (an inner join), and
+ * optionally their removal from the source (apply a blocklist, collect orphans). The other map is only ever read.
+ * One pass over the source reads a record word, the filter's field, the join bytes and one probe per candidate;
+ * only the reported entries are copied. The rules of the scan block above hold unchanged for both maps (xe_sync
+ * first, one upload of each host-dirty map, finished on return, stream NULL is the VM's stream, the same four map
+ * types are XE_ERR_UNSUPPORTED on either side, the filter and its errors are the scan's).
+ *
+ *   candidates: the entries xe_map_scan_device would report for `f` on src_map; *selected (may be NULL) = their
+ *             number.
+ *   join key: the group's rule (xe_map_group_spec from / offset / len): `len` bytes at byte `offset` of the
+ *             source entry's key (ARRAY source: its index as a u32) or value, any alignment. A nil-backed source
+ *             value reads as zeros.
+ *   present:  HASH other: an entry holds those bytes as its key (len == its key_size). A deleted key is absent; a
+ *             nil-backed entry is present and its value reads as zeros. ARRAY other: len 1, 2 or 4, little
+ *             endian, zero-extended: the index; present when below max_entries, absent at or beyond it (as for
+ *             xe_map_lookup_batch_device: no error).
+ *   kept:     the candidates that are present under XE_MJ_PRESENT, absent under XE_MJ_ABSENT. *matched = their
+ *             number, always the total (NULL: XE_ERR_INVAL).
+ *   output:   with r = min(*matched, cap_entries), the first r kept entries in ascending slot order of src_map go
+ *             to d_keys and d_values exactly as a scan writes them, and d_other_values (r x other_map's
+ *             value_size) gets the value of the entry each one joined with: zeros when that entry is nil-backed,
+ *             and always zeros under XE_MJ_ABSENT. Any of the three pointers may be NULL; no byte past entry r is
+ *             written. cap_entries 0, or all three NULL without XE_MJ_REMOVE, only counts.
+ *   remove:   XE_MJ_REMOVE, HASH src_map only (ARRAY: XE_ERR_INVAL): removes exactly the r reported entries, each
+ *             left as xe_map_expire_device leaves one; the outputs hold what was there before. Like it the call
+ *             writes the delta base of xe_map_delta and is refused with XE_ERR_INVAL while a shard epoch is
+ *             open; without the flag the call changes no state and is allowed there. With all three pointers NULL
+ *             it removes up to cap_entries kept entries silently.
+ *   self:     src_map == other_map is allowed: every probe and every output is complete before anything is
+ *             removed.
+ *   errors:   j or matched NULL, from > 1, mode > 1, an unknown flag bit, pad != 0, join bytes outside the source
+ *             key (ARRAY: 4 bytes) or value, a len that does not fit other_map as stated above, a HASH other_map
+ *             with key_size 0: XE_ERR_INVAL, and nothing changes. */
+#define XE_MJ_PRESENT 0   /* keep the source entries whose join key IS an entry of the other map */
+#define XE_MJ_ABSENT 1    /* ... whose join key is NOT */
+#define XE_MJ_REMOVE 1u   /* flags: also remove the r reported entries from src_map (HASH only) */
+typedef struct xe_map_join_spec {
+  uint32_t from;    /* XE_MG_KEY / XE_MG_VALUE: where the join bytes are read in the source entry */
+  uint32_t offset;  /* first join byte there; any alignment */
+  uint32_t len;     /* HASH other: == its key_size (1..64). ARRAY other: 1, 2 or 4; the bytes, little endian,
+                       zero-extended, are the index */
+  uint32_t mode;    /* XE_MJ_PRESENT / XE_MJ_ABSENT */
+  uint32_t flags;   /* 0 or XE_MJ_REMOVE */
+  uint32_t pad;     /* 0 */
+} xe_map_join_spec;
+int xe_map_join_device(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other_map,
+                       void* d_keys, void* d_values, void* d_other_values, uint64_t cap_entries, uint64_t* matched,
+                       uint64_t* selected, void* stream);
+/* The same with host pointers: the r reported entries are staged through device buffers of the VM. */
+int xe_map_join(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other_map,
+                void* keys, void* values, void* other_values, uint64_t cap_entries, uint64_t* matched,
+                uint64_t* selected);
+
 /* --- tombstone compaction on the device copy (HASH maps). The removing calls above (xe_map_delete_batch_device,
  * xe_map_expire*, xe_map_evict*) and the keyed path's unused reservations leave tombstones that keep their key
  * words, and every probe walks through them. xe_map_compact removes every tombstone of the table in place and
