@@ -202,6 +202,14 @@ _SIGS = {
     "map_modify_batch_device": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, C.c_uint32, P, P, P]),
     "map_modify_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, C.c_uint32, P, P]),
     "debug_map_traffic": (C.c_int, [P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lru_lookup_batch_device": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P, C.c_uint32, P]),
+    "lru_delete_batch_device": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P]),
+    "lru_order_device": (C.c_int, [P, C.c_int32, P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
+    "lru_evict_device": (C.c_int, [P, C.c_int32, P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64), P]),
+    "lru_lookup_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P, P, C.c_uint32]),
+    "lru_delete_batch": (C.c_int, [P, C.c_int32, P, C.c_uint64, P]),
+    "lru_order": (C.c_int, [P, C.c_int32, P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "lru_evict": (C.c_int, [P, C.c_int32, P, C.c_uint32, P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "multi_create": (C.c_int, [P, C.c_uint32, C.POINTER(P)]),
     "multi_destroy": (None, [P]),
     "multi_last_error": (C.c_char_p, [P]),
@@ -237,6 +245,8 @@ HEADER_SYMBOLS = [
     "xe_map_top_device", "xe_map_evict_device", "xe_map_top", "xe_map_evict", "xe_map_stats",
     "xe_map_group", "xe_map_join_device", "xe_map_join", "xe_map_compact",
     "xe_map_modify_device", "xe_map_modify", "xe_map_modify_batch_device", "xe_map_modify_batch",
+    "xe_lru_lookup_batch_device", "xe_lru_delete_batch_device", "xe_lru_order_device", "xe_lru_evict_device",
+    "xe_lru_lookup_batch", "xe_lru_delete_batch", "xe_lru_order", "xe_lru_evict",
     "xe_set_kernel_cache", "xe_kernel_source", "xe_compile_kernel_source", "xe_kernel_object_name",
     "xe_kernel_cache_stats",
     "xe_cancel", "xe_trace_config", "xe_trace_read", "xe_set_helper", "xe_reset_helper",

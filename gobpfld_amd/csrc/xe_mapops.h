@@ -1,9 +1,11 @@
 // Device-resident batched map operations (include/xdpemu.h: xe_map_lookup_batch_device,
 // xe_map_update_batch_device, xe_map_delete_batch_device, xe_map_scan_device, xe_map_expire_device,
 // xe_map_top_device, xe_map_evict_device, xe_map_stats, xe_map_group, xe_map_compact, xe_map_modify_device,
-// xe_map_modify_batch_device, xe_map_join_device): the per-key and per-slot decision logic that the kernels
+// xe_map_modify_batch_device, xe_map_join_device; xe_lru_lookup_batch_device, xe_lru_delete_batch_device,
+// xe_lru_order_device, xe_lru_evict_device): the per-key and per-slot decision logic that the kernels
 // (xe_mapops.hip) and the host simulation (the loops at the end of this file) share, and the launch
-// declaration. ARRAY and HASH maps only. Not part of the per-program kernel sources.
+// declaration. ARRAY and HASH maps; LRU_HASH maps through the xe_lru_* calls only. Not part of the per-program
+// kernel sources.
 //
 // A batch is a sequence of steps, one launch each (a step's writes are the next step's reads: the
 // phases are kernel boundaries, no workgroup waits on another):
@@ -127,9 +129,36 @@
 //                    1) goes to entry j of the third output. Behind COPY and in front of EXPIRE: a join of a map
 //                    with itself reads everything before anything is removed
 //            EXPIRE  (the scan's, under XE_MJ_REMOVE)
+//   lru      FIND, VALUE   the lookup's, over an LRU view (below): the probe is mo_find unchanged, the value of a
+//   lookup           slot is the pool value its record names, nil-backed when that value's length is 0
+//            TOUCH   (without XE_LRU_PEEK) one key per lane: a found entry raises its value's stamp to
+//                    epoch << 48 | (i + 1) (a 64-bit atomic max), the epoch a fresh one as every batch run takes:
+//                    above every stamp in the map, and the last repetition of a key wins by construction. The
+//                    links are not touched: the runtime marks them stale and lru_relink rebuilds them from the
+//                    stamps when a replay or a host read asks
+//   lru      FIND    the delete's
+//   delete   CLAIM   one CAS on word 0 from FULL | vid << 32 to TOMB | vid << 32 per present key (the high half
+//                    holds the value id and cannot name the claimer): the entry that wins marks itself in its own
+//                    slot[i] (kMoFresh); the winners are counted (kMoGone)
+//            ERASE   a winner leaves its entry as xe_interp.h lru_erase leaves one: stamp 0 (out of the usage
+//                    order), the record a plain tombstone with its key words kept; the header's count drops by the
+//                    winners once. The value bytes and the value's length stay as they are, as lru_erase leaves
+//                    them: nothing reads the pool entry of a value whose stamp is 0 and which no record names
+//                    (ordered_download walks the links, which lru_relink builds from the non-zero stamps), and
+//                    whoever hands the id out again (lru_insert) sets its length and writes its value first
+//   lru      PREFIX, PICK, CUT, SCAN, TRIM, SCAN, SCATTER   (the top's) over the table's slots and the nil key's
+//   order /          record behind them. The eligible entries are the FULL records with a non-zero stamp whose
+//   evict            value passes the filter; the rank key is the stamp (width 8), complemented when the most
+//                    recent ranks first. Equal stamps are taken in slot order (TRIM)
+//            RANK    entry j < r: the rank key of slot[j] into the sort's keys
+//            SORT    the r (rank key, slot) pairs by rank key, ascending and stable (SCATTER left them in slot
+//                    order, so equal stamps stay in slot order): the device radix sort the library links for
+//                    lru_relink; a std::stable_sort in the host simulation. COPY then reports in rank order
+//            COPY    (the scan's; the nil key's record reports key_size zero bytes)
+//            ERASE   (evict only) the delete's, every one of the r entries a winner
 //
 // The last-writer word is the high half of a HASH record's word 0 (a HASH map keeps nothing there;
-// an LRU record keeps its value id there, and LRU maps are not served) and, for an ARRAY map, a word per
+// an LRU record keeps its value id there, and the calls that mark are not served for LRU maps) and, for an ARRAY map, a word per
 // index in a buffer of the map's own that is zero between calls. Both are zero again when a call returns.
 //
 // A deleted record keeps its key words. A tombstone holding key words is what the keyed path calls a
@@ -156,11 +185,12 @@ enum : uint32_t {
   XE_MO_COMPACT_MARK, XE_MO_COMPACT_REBUILD,
   XE_MO_MODIFY_TILE, XE_MO_MODIFY_EDIT, XE_MO_MODIFY_MARK, XE_MO_MODIFY_KEYED,
   XE_MO_JOIN_SELECT, XE_MO_JOIN_VALUE,
+  XE_MO_LRU_TOUCH, XE_MO_LRU_CLAIM, XE_MO_LRU_ERASE, XE_MO_LRU_RANK, XE_MO_LRU_SORT,
   XE_MO_STEPS
 };
 
 constexpr uint32_t kMoInline = 16;           // values up to this many bytes move on their key's lane
-constexpr uint32_t kMoFresh = 0x80000000u;   // slot[i]: this entry claimed the record (update)
+constexpr uint32_t kMoFresh = 0x80000000u;   // slot[i]: this entry claimed the record (update, LRU delete)
 constexpr uint32_t kMoVlen0 = 0x40000000u;   // slot[i]: the record's value reads as zeros (lookup)
 constexpr uint32_t kMoSlotMask = 0x3fffffffu;  // (cap <= 2^27, ARRAY indices are checked against it)
 constexpr uint32_t kMoAbsent = kMoSlotMask;
@@ -195,13 +225,20 @@ static_assert(kMmTileMax >= kMoInline, "the single pass serves at least the valu
 enum : uint32_t { kMfAll = 0, kMfEq, kMfNe, kMfLt, kMfLe, kMfGt, kMfGe, kMfAnyBits, kMfNoBits, kMfOps };
 
 // One table: what a probe reads. A call's source map is the XeMapOp itself, the group's destination its `dst`.
+// An LRU view (kind XE_DM_LRU): recs, cap and rwords as for HASH (word 0 of a FULL record: XE_SLOT_FULL | value id
+// << 32; the nil key's record sits at slot cap); vals is the value pool, indexed by value id.
 struct XeMapView {
-  uint32_t kind;  // XE_DM_ARRAY / XE_DM_HASH
+  uint32_t kind;  // XE_DM_ARRAY / XE_DM_HASH / XE_DM_LRU
   uint32_t key_size, value_size, max_entries, cap, kwords, rwords;
-  uint64_t* recs;         // HASH: slot records
+  uint64_t* recs;         // HASH, LRU: slot records
   uint8_t* vals;
   uint8_t* snap;          // the delta base (HostMap::d_snap): kept equal to vals on the slots a call writes
   uint32_t* count;        // HASH: entry count
+  // LRU
+  uint32_t pool_cap;      // value ids are below it
+  uint32_t* elen;         // [pool_cap] a value's length: 0 is a nil backing
+  uint64_t* tag;          // [pool_cap] a value's stamp (xe_interp.h lru_stamp): 0 is "not in the usage order"
+  uint64_t* hdr;          // the map's header words (word 2: the entry count)
 };
 struct XeMapOp : XeMapView {
   uint32_t n;             // batch entries
@@ -238,6 +275,14 @@ struct XeMapOp : XeMapView {
   // modify
   uint32_t m_n;           // the edits in use
   xe_map_edit m_edits[XE_MM_MAX_EDITS];  // checked by the runtime: op, width, the field and an operand field inside the value
+  // lru
+  uint64_t l_stamp;       // TOUCH: the call's epoch << 48
+  uint32_t l_all;         // ERASE: 1: every one of the n entries is a winner (evict), the count drops by n
+  uint64_t* l_keys;       // [n] RANK: the rank keys of slot[0 .. n); SORT: sorted into l_keys2, the slots into l_slot2
+  uint64_t* l_keys2;
+  uint32_t* l_slot2;
+  void* l_tmp;            // SORT: the radix sort's own storage (xe_mapop_sort_bytes)
+  uint64_t l_tmp_bytes;
 };
 // The whole struct is a kernel argument. The edits add 200 bytes; it stays far below the 4 KiB a HIP kernel's
 // arguments may take.
@@ -386,6 +431,21 @@ XE_HD void mo_move(uint8_t* t, const uint8_t* s, uint32_t len, uint32_t sub, uin
     for (uint32_t j = sub; j < len; j += lanes) t[j] = s ? s[j] : uint8_t(0);
 }
 
+// ---------------------------------------------------------------- where a slot's value lies
+// The pair every value access of a map that may be an LRU one goes through, given word 0 of the slot's record
+// (ARRAY: anything): is the value nil-backed (it then reads as zeros), and its address. HASH and ARRAY: the VLEN0
+// bit and vals + slot x value_size, as before; LRU: the length and the pool entry of the value id in word 0's high
+// half (an id at or past pool_cap, which no record of a sound map holds, reads as nil and is never dereferenced).
+XE_HD uint32_t ml_vid(uint64_t w0) { return uint32_t(w0 >> 32); }
+XE_HD bool mo_val_nil(const XeMapView& v, uint64_t w0) {
+  if (v.kind == XE_DM_LRU) return ml_vid(w0) >= v.pool_cap || v.elen[ml_vid(w0)] == 0;
+  return v.kind == XE_DM_HASH && (uint32_t(w0) & XE_SLOT_VLEN0) != 0;
+}
+XE_HD uint8_t* mo_val_at(const XeMapView& v, uint32_t slot, uint64_t w0) {
+  return v.vals + uint64_t(v.kind == XE_DM_LRU ? ml_vid(w0) : slot) * v.value_size;
+}
+XE_HD uint64_t mo_word0(const XeMapView& v, uint32_t slot) { return v.kind == XE_DM_ARRAY ? 0 : v.recs[uint64_t(slot) * v.rwords]; }
+
 // ---------------------------------------------------------------- lookup / delete: find
 // Entry i's slot, read-only (kMoAbsent: absent or out of range). find: mo_find, or the kernels' faster probe.
 template <class Find>
@@ -401,18 +461,20 @@ XE_HD uint32_t mo_slot_of(const XeMapOp& o, uint32_t i, Find find) {
 // ... and what follows from it: found[i], slot[i], and a small value on the same lane.
 XE_HD void mo_find_finish(const XeMapOp& o, uint32_t i, uint32_t s, bool with_value) {
   uint32_t w = s;
-  if (s != kMoAbsent && o.kind == XE_DM_HASH && (uint32_t(o.recs[uint64_t(s) * o.rwords]) & XE_SLOT_VLEN0)) w |= kMoVlen0;
+  const uint64_t w0 = s != kMoAbsent ? mo_word0(o, s) : 0;
+  if (s != kMoAbsent && mo_val_nil(o, w0)) w |= kMoVlen0;
   o.slot[i] = w;
   if (o.found) o.found[i] = s != kMoAbsent ? 1 : 0;
   if (with_value && o.value_size <= kMoInline && o.value_size) {
     const bool zero = s == kMoAbsent || (w & kMoVlen0);
-    mo_move(o.values_out + uint64_t(i) * o.value_size, zero ? nullptr : o.vals + uint64_t(s) * o.value_size, o.value_size, 0, 1);
+    mo_move(o.values_out + uint64_t(i) * o.value_size, zero ? nullptr : mo_val_at(o, s, w0), o.value_size, 0, 1);
   }
 }
 XE_HD void mo_lookup_value_item(const XeMapOp& o, uint32_t i, uint32_t sub, uint32_t lanes) {
   const uint32_t w = o.slot[i], s = w & kMoSlotMask;
   const bool zero = s == kMoAbsent || (w & kMoVlen0);
-  mo_move(o.values_out + uint64_t(i) * o.value_size, zero ? nullptr : o.vals + uint64_t(s) * o.value_size, o.value_size, sub, lanes);
+  mo_move(o.values_out + uint64_t(i) * o.value_size, zero ? nullptr : mo_val_at(o, s, o.kind == XE_DM_LRU ? mo_word0(o, s) : 0),
+          o.value_size, sub, lanes);
 }
 
 // ---------------------------------------------------------------- update
@@ -561,14 +623,10 @@ XE_HD uint64_t ms_field(const uint8_t* v, uint32_t width) {
 // value and never matches); a nil-backed value reads as zeros, as it does for xe_map_lookup.
 XE_HD bool ms_select_item(const XeMapOp& o, uint32_t s) {
   const uint32_t at = o.sbase + s;
-  bool zero = false;
-  if (o.kind == XE_DM_HASH) {
-    const uint32_t st = uint32_t(o.recs[uint64_t(at) * o.rwords]);
-    if (!(st & XE_SLOT_FULL)) return false;
-    zero = (st & XE_SLOT_VLEN0) != 0;
-  }
+  const uint64_t w0 = mo_word0(o, at);
+  if (o.kind != XE_DM_ARRAY && !(uint32_t(w0) & XE_SLOT_FULL)) return false;
   if (o.f_op == kMfAll) return true;
-  return ms_filter(o.f_op, zero ? 0 : ms_field(o.vals + uint64_t(at) * o.value_size + o.f_off, o.f_width), o.f_operand);
+  return ms_filter(o.f_op, mo_val_nil(o, w0) ? 0 : ms_field(mo_val_at(o, at, w0) + o.f_off, o.f_width), o.f_operand);
 }
 // Lane `lane` of round `round` of tile t, given the round's bitmap word and the matches in front of the
 // round: a selected slot's rank; below n it is reported.
@@ -587,14 +645,15 @@ XE_HD void ms_copy_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t lan
     if (o.kind == XE_DM_ARRAY) {
       uint8_t* k = o.keys_out + uint64_t(j) * 4;
       if (sub == 0) k[0] = uint8_t(s), k[1] = uint8_t(s >> 8), k[2] = uint8_t(s >> 16), k[3] = uint8_t(s >> 24);
-    } else if (o.key_size) {
-      mo_move(o.keys_out + uint64_t(j) * o.key_size, reinterpret_cast<const uint8_t*>(o.recs + uint64_t(s) * o.rwords + 1),
+    } else if (o.key_size) {  // (an LRU map's nil key, the record past the table: key_size zero bytes)
+      const bool nil_key = o.kind == XE_DM_LRU && s == o.cap;
+      mo_move(o.keys_out + uint64_t(j) * o.key_size, nil_key ? nullptr : reinterpret_cast<const uint8_t*>(o.recs + uint64_t(s) * o.rwords + 1),
               o.key_size, sub, lanes);
     }
   }
   if (o.values_out) {
-    const bool zero = o.kind == XE_DM_HASH && (uint32_t(o.recs[uint64_t(s) * o.rwords]) & XE_SLOT_VLEN0);
-    mo_move(o.values_out + uint64_t(j) * o.value_size, zero ? nullptr : o.vals + uint64_t(s) * o.value_size, o.value_size, sub, lanes);
+    const uint64_t w0 = mo_word0(o, s);
+    mo_move(o.values_out + uint64_t(j) * o.value_size, mo_val_nil(o, w0) ? nullptr : mo_val_at(o, s, w0), o.value_size, sub, lanes);
   }
 }
 XE_HD void ms_expire_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t lanes) {
@@ -626,15 +685,15 @@ XE_HD uint64_t mt_mask(uint32_t width) { return width >= 8 ? ~uint64_t(0) : (uin
 // VLEN0), complemented within the width when the largest ranks first.
 XE_HD bool mt_key_item(const XeMapOp& o, uint32_t s, uint64_t* key) {
   const uint32_t at = o.sbase + s;
-  bool zero = false;
-  if (o.kind == XE_DM_HASH) {
-    const uint32_t st = uint32_t(o.recs[uint64_t(at) * o.rwords]);
-    if (!(st & XE_SLOT_FULL)) return false;
-    zero = (st & XE_SLOT_VLEN0) != 0;
-  }
-  const uint8_t* v = o.vals + uint64_t(at) * o.value_size;
+  const uint64_t w0 = mo_word0(o, at);
+  if (o.kind != XE_DM_ARRAY && !(uint32_t(w0) & XE_SLOT_FULL)) return false;
+  // an LRU entry ranks by its stamp (t_width is 8), and one whose stamp is 0 is in no usage order
+  const uint64_t stamp = o.kind == XE_DM_LRU && ml_vid(w0) < o.pool_cap ? o.tag[ml_vid(w0)] : 0;
+  if (o.kind == XE_DM_LRU && !stamp) return false;
+  const bool zero = mo_val_nil(o, w0);
+  const uint8_t* v = mo_val_at(o, at, w0);
   if (o.f_op != kMfAll && !ms_filter(o.f_op, zero ? 0 : ms_field(v + o.f_off, o.f_width), o.f_operand)) return false;
-  const uint64_t f = zero ? 0 : ms_field(v + o.t_off, o.t_width);
+  const uint64_t f = o.kind == XE_DM_LRU ? stamp : zero ? 0 : ms_field(v + o.t_off, o.t_width);
   *key = o.t_desc ? ~f & mt_mask(o.t_width) : f;
   return true;
 }
@@ -979,9 +1038,50 @@ XE_HD void mj_value_item(const XeMapOp& o, uint32_t j, uint32_t sub, uint32_t la
           o.dst.value_size, sub, lanes);
 }
 
+// ---------------------------------------------------------------- lru
+// TOUCH, entry i: a found entry's value gets the call's stamp for it. A later repetition of the key carries a
+// larger one, so the maximum is the last occurrence's.
+XE_HD void ml_touch_item(const XeMapOp& o, uint32_t i) {
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (s == kMoAbsent) return;
+  const uint32_t vid = ml_vid(o.recs[uint64_t(s) * o.rwords]);
+  if (vid < o.pool_cap) mo_max64(o.tag + vid, o.l_stamp | (uint64_t(i) + 1));
+}
+// CLAIM, entry i: true when this entry took the record (the caller counts the winners).
+XE_HD bool ml_claim_item(const XeMapOp& o, uint32_t i) {
+  const uint32_t s = o.slot[i] & kMoSlotMask;
+  if (s == kMoAbsent) return false;
+  uint64_t* r = o.recs + uint64_t(s) * o.rwords;
+  const uint64_t w0 = mo_load64(r);
+  if (!(uint32_t(w0) & XE_SLOT_FULL)) return false;  // a repetition of the key has it
+  if (mo_cas64(r, w0, (w0 & ~uint64_t(0xffffffffu)) | XE_SLOT_TOMB) != w0) return false;
+  o.slot[i] |= kMoFresh;
+  return true;
+}
+// ERASE, entry i: what lru_erase leaves (the head of this file says why the value bytes stay).
+XE_HD void ml_erase_item(const XeMapOp& o, uint32_t i) {
+  if (i == 0) o.hdr[2] -= o.l_all ? o.n : o.ctr[kMoGone];
+  const uint32_t w = o.slot[i];
+  if (!o.l_all && !(w & kMoFresh)) return;
+  uint64_t* r = o.recs + uint64_t(w & kMoSlotMask) * o.rwords;
+  const uint32_t vid = ml_vid(r[0]);
+  if (vid < o.pool_cap) o.tag[vid] = 0;
+  r[0] = XE_SLOT_TOMB;  // a plain tombstone, its key words kept
+}
+// RANK, entry j: the rank key of slot[j] (SCATTER selected it: it is eligible).
+XE_HD void ml_rank_item(const XeMapOp& o, uint32_t j) {
+  uint64_t key = 0;
+  mt_key_item(o, o.slot[j] - o.sbase, &key);
+  o.l_keys[j] = key;
+}
+
 #ifndef XE_HOSTSIM
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream);
+extern "C" int xe_mapop_sort_bytes(uint32_t n, size_t* bytes);  // SORT's l_tmp for n pairs
 #else
+#include <algorithm>
+#include <vector>
+static inline int xe_mapop_sort_bytes(uint32_t, size_t* bytes) { *bytes = 8; return 0; }
 // The host simulation: the same items, one after another. A pass that ballots: for every tile, round and lane
 // cls(t, r, lane) gives the slot's class; done(t, w1, w2, c1, c2) gets the tile's words of class 1 and class 2,
 // one per round, and their counts.
@@ -1148,6 +1248,13 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
     }
     return 0;
   }
+  if (step == XE_MO_LRU_SORT) {
+    std::vector<uint32_t> idx(o.n);
+    for (uint32_t j = 0; j < o.n; j++) idx[j] = j;
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return o.l_keys[a] < o.l_keys[b]; });
+    for (uint32_t j = 0; j < o.n; j++) o.l_keys2[j] = o.l_keys[idx[j]], o.l_slot2[j] = o.slot[idx[j]];
+    return 0;
+  }
   if (step == XE_MO_MODIFY_TILE) {
     for (uint32_t s = 0; s < o.nslots; s++)
       if (ms_select_item(o, s)) mm_modify_item(o, o.sbase + s, 0, 1, false), o.ctr[kMoMatched]++;
@@ -1170,6 +1277,10 @@ static inline int xe_launch_mapop(const XeMapOp* op, uint32_t step, void*) {
       case XE_MO_MODIFY_MARK: mm_mark_item(o, i); break;
       case XE_MO_MODIFY_KEYED: mm_keyed_item(o, i, 0, 1); break;
       case XE_MO_JOIN_VALUE: mj_value_item(o, i, 0, 1, mo_find); break;
+      case XE_MO_LRU_TOUCH: ml_touch_item(o, i); break;
+      case XE_MO_LRU_CLAIM: if (ml_claim_item(o, i)) o.ctr[kMoGone]++; break;
+      case XE_MO_LRU_ERASE: ml_erase_item(o, i); break;
+      case XE_MO_LRU_RANK: ml_rank_item(o, i); break;
       default: return -1;
     }
   }

@@ -4,12 +4,16 @@
 // destination allow it). Scan and expire add one wave per tile of slots (SELECT, SCATTER) and a
 // one-workgroup prefix sum of the tile counts (SCAN); their COPY and EXPIRE are value kernels.
 //
+// The xe_lru_* calls run the same kernels over an LRU view and add four lane steps (TOUCH, CLAIM, ERASE, RANK) and
+// SORT, the library's device radix sort over the r selected (rank key, slot) pairs.
+//
 // 256-thread workgroups. Up to kMoOneTurn of them take one entry (or one sub-group's entry) per lane:
 // 65,536 keys in a lane step. A larger batch gets a quarter of the workgroups it would need for that, at
 // least kMoOneTurn and at most kMoMaxBlocks, and its lanes stride on: the probes of a large batch are
 // latency-bound, and a lane that walks four keys amortises its launch while 4 to 8 workgroups per CU
 // stay resident to overlap the round trips.
 #include <hip/hip_runtime.h>
+#include <hipcub/device/device_radix_sort.hpp>
 
 #include "xe_mapops.h"
 
@@ -84,9 +88,13 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_lane_kernel(XeMapOp o, ui
   uint32_t i = blockIdx.x * kMoThreads + threadIdx.x;
   for (uint32_t t = 0; t < turns; t++, i += stride) {
     const bool in = i < o.n;  // (n <= 2^32 - 2^17: i does not wrap)
-    bool fresh = false;
+    bool fresh = false, gone = false;
     if (in) {
       switch (step) {
+        case XE_MO_LRU_TOUCH: ml_touch_item(o, i); break;
+        case XE_MO_LRU_CLAIM: gone = ml_claim_item(o, i); break;
+        case XE_MO_LRU_ERASE: ml_erase_item(o, i); break;
+        case XE_MO_LRU_RANK: ml_rank_item(o, i); break;
         case XE_MO_LOOKUP_FIND: mo_find_finish(o, i, mo_slot_of(o, i, find_slot), true); break;
         case XE_MO_DELETE_FIND: mo_find_finish(o, i, mo_slot_of(o, i, find_slot), false); break;
         case XE_MO_UPDATE_LOCATE: fresh = mo_update_locate_item(o, i); break;
@@ -98,6 +106,7 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapop_lane_kernel(XeMapOp o, ui
       }
     }
     if (step == XE_MO_UPDATE_LOCATE) count_once_per_wave(o.ctr + kMoNew, fresh);  // the claims
+    if (step == XE_MO_LRU_CLAIM) count_once_per_wave(o.ctr + kMoGone, gone);      // the winners
   }
 }
 
@@ -561,8 +570,9 @@ __global__ void __launch_bounds__(kMoThreads) xe_mapjoin_value_kernel(XeMapOp o,
 // xe_mo_lanes lanes (the kernel's second argument is the step; a value step's kernel is the instantiation for
 // those lanes; kValueDst: the join's value kernel, the lanes by the other map's value size). kTileSrc /
 // kTileDst: a wave per tile of the source's slots (the second argument is their number) / of the group's
-// destination table, a HASH one (the step). kOneGroup: one workgroup, once the source has a tile.
-enum MoShape : uint32_t { kNoShape = 0, kLane, kValue, kValueDst, kTileSrc, kTileDst, kOneGroup };
+// destination table, a HASH one (the step). kOneGroup: one workgroup, once the source has a tile. kSort: no kernel
+// of this file's, the device radix sort over the n pairs.
+enum MoShape : uint32_t { kNoShape = 0, kLane, kValue, kValueDst, kTileSrc, kTileDst, kOneGroup, kSort };
 using MoKernel = void (*)(XeMapOp, uint32_t);
 struct MoStep {
   MoShape shape;
@@ -574,7 +584,7 @@ struct MoTable {
 constexpr MoTable mo_table() {
   MoTable t{};
   for (uint32_t s : {XE_MO_LOOKUP_FIND, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, XE_MO_UPDATE_MARK, XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM,
-                     XE_MO_MODIFY_MARK})
+                     XE_MO_MODIFY_MARK, XE_MO_LRU_TOUCH, XE_MO_LRU_CLAIM, XE_MO_LRU_ERASE, XE_MO_LRU_RANK})
     t.row[s] = {kLane, xe_mapop_lane_kernel};
   for (uint32_t s : {XE_MO_LOOKUP_VALUE, XE_MO_UPDATE_COPY, XE_MO_DELETE_ZERO, XE_MO_SCAN_COPY, XE_MO_SCAN_EXPIRE, XE_MO_MODIFY_EDIT,
                      XE_MO_MODIFY_KEYED})
@@ -595,12 +605,13 @@ constexpr MoTable mo_table() {
   t.row[XE_MO_MODIFY_TILE] = {kTileSrc, xe_mapmodify_tile_kernel};
   t.row[XE_MO_JOIN_SELECT] = {kTileSrc, xe_mapjoin_select_kernel};
   t.row[XE_MO_JOIN_VALUE] = {kValueDst, nullptr};
+  t.row[XE_MO_LRU_SORT] = {kSort, nullptr};
   return t;
 }
 constexpr MoTable kMoSteps = mo_table();
 constexpr bool mo_steps_filled() {
   for (const MoStep& r : kMoSteps.row)
-    if (r.shape == kNoShape || (r.kernel == nullptr) != (r.shape == kValue || r.shape == kValueDst)) return false;
+    if (r.shape == kNoShape || (r.kernel == nullptr) != (r.shape == kValue || r.shape == kValueDst || r.shape == kSort)) return false;
   return true;
 }
 static_assert(sizeof kMoSteps.row / sizeof kMoSteps.row[0] == XE_MO_STEPS && mo_steps_filled(), "one filled row per step");
@@ -611,13 +622,31 @@ uint32_t mo_blocks(uint64_t want) {
   return uint32_t(want <= kMoOneTurn ? want : want / 4 < kMoOneTurn ? kMoOneTurn : want / 4 < kMoMaxBlocks ? want / 4 : kMoMaxBlocks);
 }
 
+// SORT: (l_keys, slot) -> (l_keys2, l_slot2) by rank key, ascending. The LSD radix sort is stable, so equal keys
+// keep the slot order SCATTER left them in.
+int mo_sort(const XeMapOp& o, hipStream_t s) {
+  size_t tmp = o.l_tmp_bytes;
+  return hipcub::DeviceRadixSort::SortPairs(o.l_tmp, tmp, (const unsigned long long*)o.l_keys, (unsigned long long*)o.l_keys2,
+                                            (const uint32_t*)o.slot, o.l_slot2, int(o.n), 0, 64, s) == hipSuccess ? 0 : -1;
+}
+
 }  // namespace
+
+extern "C" int xe_mapop_sort_bytes(uint32_t n, size_t* bytes) {
+  size_t tmp = 0;
+  if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, int(n), 0, 64, nullptr) != hipSuccess)
+    return -1;
+  *bytes = tmp ? tmp : 8;
+  return 0;
+}
 
 extern "C" int xe_launch_mapop(const XeMapOp* op, uint32_t step, void* stream) {
   if (step >= XE_MO_STEPS) return -1;
   const MoShape shape = kMoSteps.row[step].shape;
   MoKernel kernel = kMoSteps.row[step].kernel;
   uint32_t blocks = 1, arg = step;
+  if (shape == kSort) return op->n ? mo_sort(*op, hipStream_t(stream)) : 0;
   if (shape == kLane || shape == kValue || shape == kValueDst) {
     if (!op->n) return 0;
     const uint32_t lanes = shape == kValue ? xe_mo_lanes(op->value_size) : shape == kValueDst ? xe_mo_lanes(op->dst.value_size) : 1;

@@ -1323,6 +1323,7 @@ int map_download(xe_vm* vm, HostMap& m) {
     if (m.dkind == XE_DM_LRU && lru_relink(vm, m, vm->stream)) return -1;
     if (ordered_download(vm, m)) return -1;
     m.dev_dirty = false;
+    m.downloads++;
     return 0;
   }
   if (d2h(m.vals.data(), m.d_vals, m.vals_alloc, vm->stream)) return -1;
@@ -1460,6 +1461,7 @@ int ordered_upload(xe_vm* vm, HostMap& m, uint64_t slack, uint64_t slack_bytes) 
   if (!m.d_hdr && dev_alloc((void**)&m.d_hdr, 8 * 8)) return -1;
   if (h2d(m.d_hdr, hdr.data(), 64, st) || dsync(st)) return -1;
   m.host_dirty = false;
+  m.uploads++;
   return 0;
 }
 
@@ -4985,6 +4987,196 @@ int xe_map_evict(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_ord
 }
 int xe_map_stats(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
   return map_stats_run(vm, mi, f, field, out, stream);
+}
+
+// ---- LRU_HASH maps on the device copy (xe_mapops.h: the lru steps over an LRU view). The stamps are current
+// between calls (replicas folded after each launch, the one-lane replay writes them itself, an upload writes
+// ranks); the links are not needed here and are left to lru_relink.
+static XeMapView lru_view(const HostMap& m) {
+  XeMapView v{};
+  v.kind = XE_DM_LRU;
+  v.key_size = m.def.key_size;
+  v.value_size = m.def.value_size;
+  v.max_entries = m.def.max_entries;
+  v.cap = m.cap;
+  v.kwords = m.kwords;
+  v.rwords = xe_hash_rwords(m.kwords);
+  v.recs = m.d_keys;
+  v.vals = m.d_vals;
+  v.pool_cap = m.pool_cap;
+  v.elen = m.d_elen;
+  v.tag = m.d_tag;
+  v.hdr = m.d_hdr;
+  return v;
+}
+// mapop_begin for an LRU map. 1: nothing to do (count 0).
+static int lru_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, MapOpCall& c) {
+  if (!vm) return XE_ERR_INVAL;
+  if (int rc = xe_sync(vm)) return rc;
+  c.m = get_map(vm, mi);
+  if (!c.m) return fail(vm, XE_ERR_INVAL, "map index out of bounds");
+  if (c.m->dkind != XE_DM_LRU) return fail(vm, XE_ERR_INVAL, "the xe_lru_ calls serve LRU_HASH maps only");
+  if (writes && vm->epoch_open) return fail(vm, XE_ERR_INVAL, "map writes are refused while a shard epoch is open");
+  if (count > kMoMaxCount) return fail(vm, XE_ERR_INVAL, "batched map operation: more than 2^31 keys");
+  if (set_device(vm->settings.device)) return fail(vm, XE_ERR_DEVICE, "hipSetDevice failed");
+  c.s = stream ? (xe_stream_t)stream : vm->stream;
+  if (!count) return 1;
+  if (int rc = mapop_current(vm, c.m)) return rc;
+  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(count) * 4) || dmemset(vm->d_mo, 0, kMoCounters * 4, c.s))
+    return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  static_cast<XeMapView&>(c.o) = lru_view(*c.m);
+  c.o.n = uint32_t(count);
+  c.o.ctr = (uint32_t*)vm->d_mo;
+  c.o.slot = c.o.ctr + kMoCounters;
+  return XE_OK;
+}
+// A call changed the usage order or removed entries: only the stamps say so until lru_relink runs.
+static void lru_written(xe_vm* vm, HostMap* m) {
+  m->links_stale = true;
+  map_written(vm, m);
+}
+
+int xe_lru_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_values, void* d_found,
+                               uint32_t flags, void* stream) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const bool promote = !(flags & XE_LRU_PEEK);
+  const int rc = lru_begin(vm, mi, (d_keys && d_values) ? count : 0, promote, stream, c);
+  if (rc < 0) return rc;
+  if (flags & ~XE_LRU_PEEK) return fail(vm, XE_ERR_INVAL, "lru lookup: unknown flag");
+  if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
+  if (rc == 1) return XE_OK;
+  o.keys = (const uint8_t*)d_keys;
+  o.values_out = (uint8_t*)d_values;
+  o.found = (uint8_t*)d_found;
+  if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
+  if (o.value_size > kMoInline)
+    if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s)) return r;
+  if (promote) {  // a fresh run epoch, as a batch run takes one (BatchRun::prepare): above every stamp in the map
+    if (vm->lru_epoch >= kLruEpochMax && lru_renumber(vm, s)) return fail(vm, XE_ERR_DEVICE, "LRU renumber");
+    o.l_stamp = (++vm->lru_epoch) << 48;
+    if (int r = mapop_steps(vm, o, {XE_MO_LRU_TOUCH}, s)) return r;
+  }
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "lru lookup batch");
+  if (promote) lru_written(vm, m);
+  return XE_OK;
+}
+
+int xe_lru_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_found, void* stream) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = lru_begin(vm, mi, d_keys ? count : 0, true, stream, c);
+  if (rc < 0) return rc;
+  if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
+  if (rc == 1) return XE_OK;
+  o.keys = (const uint8_t*)d_keys;
+  o.found = (uint8_t*)d_found;
+  if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND, XE_MO_LRU_CLAIM, XE_MO_LRU_ERASE}, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "lru delete batch");
+  lru_written(vm, m);
+  return XE_OK;
+}
+
+int xe_lru_lookup_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, void* values, uint8_t* found, uint32_t flags) {
+  if (!vm) return XE_ERR_INVAL;
+  HostMap* m = get_map(vm, mi);
+  if (!m || m->dkind != XE_DM_LRU || !count || !keys || !values || count > kMoMaxCount || (flags & ~XE_LRU_PEEK) ||
+      (!(flags & XE_LRU_PEEK) && vm->epoch_open))
+    return xe_lru_lookup_batch_device(vm, mi, keys, count, values, found, flags, nullptr);
+  if (int rc = stage_in(vm, m, count, keys, nullptr, true, true)) return rc;
+  if (int rc = xe_lru_lookup_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_vals, vm->d_mo_found, flags, nullptr)) return rc;
+  return stage_out(vm, m, count, values, found);
+}
+
+int xe_lru_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, uint8_t* found) {
+  if (!vm) return XE_ERR_INVAL;
+  HostMap* m = get_map(vm, mi);
+  if (!m || m->dkind != XE_DM_LRU || !count || !keys || count > kMoMaxCount || vm->epoch_open)
+    return xe_lru_delete_batch_device(vm, mi, keys, count, found, nullptr);
+  if (int rc = stage_in(vm, m, count, keys, nullptr, false, true)) return rc;
+  if (int rc = xe_lru_delete_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_found, nullptr)) return rc;
+  return stage_out(vm, m, count, nullptr, found);
+}
+
+// Order and evict: the top's selection with the stamp as the rank key (everything up to the final SCAN queued
+// without a readback), then SCATTER, RANK and SORT put the r selected slots in rank order for COPY and ERASE.
+static int lru_order_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* keys, void* values, uint64_t k,
+                         uint64_t* matched, void* stream, bool evict, bool host) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const int rc = lru_begin(vm, mi, 1, evict, host ? nullptr : stream, c);  // (the counters; slots come with r)
+  if (rc < 0) return rc;
+  if (flags & ~XE_LRU_OLDEST_FIRST) return fail(vm, XE_ERR_INVAL, "lru order: unknown flag");
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  if (m->def.key_size) o.nslots = m->cap + 1;  // the table and the nil key's record behind it
+  o.t_off = 0;
+  o.t_width = 8;
+  o.t_desc = (flags & XE_LRU_OLDEST_FIRST) ? 0 : 1;
+  *matched = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (int e = scan_scratch(vm, o, tiles, true, true)) return e;
+  o.t_k = uint32_t(std::min<uint64_t>(k, 0xffffffffu));  // (more than any table holds)
+  const char* what = evict ? "lru evict" : "lru order";
+  if (dmemset(o.bins, 0, kMtBins * 4, s)) return fail(vm, XE_ERR_DEVICE, what);
+  for (o.t_pass = 0; o.t_pass < o.t_width; o.t_pass++)
+    if (int e = mapop_steps(vm, o, {XE_MO_TOP_PREFIX, XE_MO_TOP_PICK}, s)) return e;
+  XeMapOp eq = o;  // the scan's SCAN over the equal counts
+  eq.tile = o.tile2;
+  if (int e = mapop_steps(vm, o, {XE_MO_TOP_CUT}, s)) return e;
+  if (int e = mapop_steps(vm, eq, {XE_MO_SCAN_SCAN}, s)) return e;
+  if (int e = mapop_steps(vm, o, {XE_MO_TOP_TRIM, XE_MO_SCAN_SCAN}, s)) return e;
+  uint32_t ctr[kMoCounters];
+  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+  *matched = ctr[kMtMatched];
+  const uint32_t r = ctr[kMoMatched];
+  if (!r || (!evict && !keys && !values)) return XE_OK;
+  // the r entries: slots, the sort's keys and outputs and its own storage, the staging of a host call
+  const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size;
+  const size_t k8 = (size_t(r) * 8 + 255) & ~size_t(255), s4 = (size_t(r) * 4 + 255) & ~size_t(255);
+  size_t tmp = 0;
+  if (xe_mapop_sort_bytes(r, &tmp) || ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4) ||
+      ensure_buf(&vm->d_relink, &vm->d_relink_cap, 2 * k8 + s4 + tmp))
+    return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  if (host && ((keys && ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb)) || (values && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb))))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  o.ctr = (uint32_t*)vm->d_mo;
+  o.slot = o.ctr + kMoCounters;
+  o.n = r;
+  o.l_keys = (uint64_t*)vm->d_relink;
+  o.l_keys2 = (uint64_t*)((uint8_t*)vm->d_relink + k8);
+  o.l_slot2 = (uint32_t*)((uint8_t*)vm->d_relink + 2 * k8);
+  o.l_tmp = (uint8_t*)vm->d_relink + 2 * k8 + s4;
+  o.l_tmp_bytes = tmp;
+  o.keys_out = (uint8_t*)(!keys ? nullptr : host ? vm->d_mo_keys : keys);
+  o.values_out = (uint8_t*)(!values ? nullptr : host ? vm->d_mo_vals : values);
+  if (int e = mapop_steps(vm, o, {XE_MO_SCAN_SCATTER, XE_MO_LRU_RANK, XE_MO_LRU_SORT}, s)) return e;
+  o.slot = o.l_slot2;  // rank order from here on
+  if (keys || values)
+    if (int e = mapop_steps(vm, o, {XE_MO_SCAN_COPY}, s)) return e;
+  if (evict) {
+    o.l_all = 1;
+    if (int e = mapop_steps(vm, o, {XE_MO_LRU_ERASE}, s)) return e;
+  }
+  if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s))))
+    return fail(vm, XE_ERR_DEVICE, "map operation staging");
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+  if (evict) lru_written(vm, m);
+  return XE_OK;
+}
+int xe_lru_order_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* d_keys, void* d_values, uint64_t k,
+                        uint64_t* matched, void* stream) {
+  return lru_order_run(vm, mi, f, flags, d_keys, d_values, k, matched, stream, false, false);
+}
+int xe_lru_evict_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* d_keys, void* d_values, uint64_t k,
+                        uint64_t* matched, void* stream) {
+  return lru_order_run(vm, mi, f, flags, d_keys, d_values, k, matched, stream, true, false);
+}
+int xe_lru_order(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* keys, void* values, uint64_t k, uint64_t* matched) {
+  return lru_order_run(vm, mi, f, flags, keys, values, k, matched, nullptr, false, true);
+}
+int xe_lru_evict(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* keys, void* values, uint64_t k, uint64_t* matched) {
+  return lru_order_run(vm, mi, f, flags, keys, values, k, matched, nullptr, true, true);
 }
 
 int xe_debug_map_traffic(xe_vm* vm, int32_t mi, uint64_t* uploads, uint64_t* downloads) {

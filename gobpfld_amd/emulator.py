@@ -89,6 +89,8 @@ class MapEdit:
 
 MG_KEY, MG_VALUE, MG_NONE = 0, 1, 0xffffffff  # XE_MG_* (include/xdpemu.h)
 MC_COUNT_ONLY = 1  # XE_MC_COUNT_ONLY
+LRU_PEEK = 1  # XE_LRU_PEEK (VM.lru_lookup_batch)
+LRU_OLDEST_FIRST = 1  # XE_LRU_OLDEST_FIRST (VM.lru_order / VM.lru_evict)
 
 
 @dataclass
@@ -637,6 +639,75 @@ class VM:
         info = N.MapCompactInfo()
         self._check(self.lib.map_compact(self.h, m, MC_COUNT_ONLY if count_only else 0, C.byref(info), None), "map compact")
         return {"tombstones": info.tombstones, "moved": info.moved, "longest_run": info.longest_run, "via_host": info.via_host}
+
+    # ---- LRU_HASH maps on the device copy (xe_lru_*): lookup, delete, the usage order and eviction by it
+    def lru_lookup_batch(self, m: int, keys, peek: bool = False):
+        """(values[n, value_size], found[n]) of n keys of LRU_HASH map `m`, read from the device copy. Without
+        `peek` the found keys are promoted as map_lookup key by key in order promotes them."""
+        d = self.map_defs[m]
+        k, n = self._mo_keys(m, keys)
+        flags = LRU_PEEK if peek else 0
+        if self._is_dev(k):
+            import torch
+            vals = torch.empty((n, d.value_size), dtype=torch.uint8, device=k.device)
+            found = torch.empty(n, dtype=torch.uint8, device=k.device)
+            rc = self.lib.lru_lookup_batch_device(self.h, m, k.data_ptr() or None, n, vals.data_ptr() or None,
+                                                  found.data_ptr() or None, flags, None)
+        else:
+            vals = np.zeros((n, d.value_size), dtype=np.uint8)
+            found = np.zeros(n, dtype=np.uint8)
+            rc = self.lib.lru_lookup_batch(self.h, m, k.ctypes.data, n, vals.ctypes.data, found.ctypes.data, flags)
+        self._check(rc, "lru lookup batch")
+        return vals, found
+
+    def lru_delete_batch(self, m: int, keys):
+        """Delete n keys of LRU_HASH map `m` on the device copy; found[n] = the key was present before the call."""
+        k, n = self._mo_keys(m, keys)
+        if self._is_dev(k):
+            import torch
+            found = torch.empty(n, dtype=torch.uint8, device=k.device)
+            rc = self.lib.lru_delete_batch_device(self.h, m, k.data_ptr() or None, n, found.data_ptr() or None, None)
+        else:
+            found = np.zeros(n, dtype=np.uint8)
+            rc = self.lib.lru_delete_batch(self.h, m, k.ctypes.data, n, found.ctypes.data)
+        self._check(rc, "lru delete batch")
+        return found
+
+    def _lru_order(self, m: int, k: int, flt, oldest_first: bool, on_device: bool, evict: bool):
+        d = self.map_defs[m]
+        what = "lru evict" if evict else "lru order"
+        dev_fn = self.lib.lru_evict_device if evict else self.lib.lru_order_device
+        host_fn = self.lib.lru_evict if evict else self.lib.lru_order
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        fp = None if cf is None else C.byref(cf)
+        flags = LRU_OLDEST_FIRST if oldest_first else 0
+        k = min(int(k), d.max_entries)  # (no more entries than the map holds come back)
+        n = C.c_uint64(0)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.settings.device)
+            torch.cuda.current_stream(dev).synchronize()
+            keys = torch.empty((k, d.key_size), dtype=torch.uint8, device=dev)
+            vals = torch.empty((k, d.value_size), dtype=torch.uint8, device=dev)
+            rc = dev_fn(self.h, m, fp, flags, keys.data_ptr() or None, vals.data_ptr() or None, k, C.byref(n), None)
+        else:
+            keys = np.zeros((k, d.key_size), dtype=np.uint8)
+            vals = np.zeros((k, d.value_size), dtype=np.uint8)
+            rc = host_fn(self.h, m, fp, flags, keys.ctypes.data if k else None, vals.ctypes.data if k else None, k, C.byref(n))
+        self._check(rc, what)
+        r = min(int(n.value), k)
+        return keys[:r], vals[:r], int(n.value)
+
+    def lru_order(self, m: int, k: int, flt: "MapFilter | None" = None, oldest_first: bool = False, on_device: bool = False):
+        """(keys[r, key_size], values[r, value_size], matched): the r = min(k, matched) entries of LRU_HASH map
+        `m` whose value satisfies `flt` (None: all) that were used most recently (oldest_first: least recently),
+        in that order, read from the device copy. on_device: CUDA tensors instead of numpy arrays."""
+        return self._lru_order(m, k, flt, oldest_first, on_device, False)
+
+    def lru_evict(self, m: int, k: int, flt: "MapFilter | None" = None, oldest_first: bool = True, on_device: bool = False):
+        """lru_order that also removes the r entries it returns; by default the least recently used, the
+        map's own eviction rule applied k times."""
+        return self._lru_order(m, k, flt, oldest_first, on_device, True)
 
     def map_traffic(self, m: int) -> tuple[int, int]:
         """xe_debug_map_traffic: (uploads, downloads) of the whole map so far."""

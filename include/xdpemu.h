@@ -693,6 +693,60 @@ typedef struct xe_map_compact_info {
 } xe_map_compact_info;
 int xe_map_compact(xe_vm* vm, int32_t map_idx, uint32_t flags, xe_map_compact_info* info, void* stream);
 
+/* --- LRU_HASH maps on the device copy: lookup, delete, the usage order and eviction by it, by kernels that read
+ * the map's records, values and usage stamps where they lie. Nothing of the map crosses to the host, where
+ * xe_map_lookup / _delete / _lru_order / _dump / _count first bring the whole map to the host mirror and the next
+ * batch uploads it again. The calls above keep refusing LRU_HASH (XE_ERR_UNSUPPORTED): an LRU lookup changes the
+ * usage order unless asked not to, and order / evict rank by recency and report in rank order.
+ *
+ * The rules of the batched block hold (xe_sync first; a host-dirty map is uploaded once; finished on return;
+ * stream NULL is the VM's stream; every d_* is a device address, a host address in the host-simulation build;
+ * more than 2^31 keys: XE_ERR_INVAL). A map that is not LRU_HASH is XE_ERR_INVAL, as for xe_map_lru_order; so is
+ * an unknown flag bit. The calls that write (a lookup without XE_LRU_PEEK, delete, evict) are refused with
+ * XE_ERR_INVAL while a shard epoch is open.
+ *
+ *   lookup: d_found[i] (may be NULL) and value i are what xe_map_lookup returns for key i: zeros for an absent
+ *           key or an entry whose backing is nil. count 0 does nothing. Without XE_LRU_PEEK the UsageList
+ *           afterwards is the one that xe_map_lookup for i = 0 .. count-1 in order leaves: every found key ahead
+ *           of every key not looked up, among the found keys the one whose last occurrence in the batch is latest
+ *           first, the others in their old relative order. With XE_LRU_PEEK no state changes (allowed during a
+ *           shard epoch).
+ *   delete: d_found[i] (may be NULL) = the key was present before the call, the same for every repetition;
+ *           afterwards the key is absent, the count has dropped by the distinct present keys and the remaining
+ *           UsageList order is unchanged.
+ *   order:  the eligible entries are the live entries whose value satisfies f (the scan's filter and its errors; f
+ *           NULL: every entry; a nil-backed value reads as zeros). *matched = their number (NULL: XE_ERR_INVAL).
+ *           The r = min(k, matched) that rank first by recency go to d_keys (r x key_size) and d_values
+ *           (r x value_size) in rank order: entry 0 is the most recently used, or the least recently used under
+ *           XE_LRU_OLDEST_FIRST. Either pointer may be NULL; no byte past entry r is written; k = 0 only counts.
+ *           With f NULL and k >= the count, d_keys is byte for byte what xe_map_lru_order writes (an entry under
+ *           the nil key: key_size zero bytes). Entries with equal stamps (none of the map's own calls makes them)
+ *           rank in ascending slot order: the answer is a function of the map's state. Changes no state.
+ *   evict:  removes exactly the r entries that order reports for the same arguments and reports their keys and
+ *           their values from before. With XE_LRU_OLDEST_FIRST and f NULL this is the map's own eviction rule
+ *           (maps_hash_lru.go:114-119) applied k times.
+ *
+ * Not here: a device-side LRU update batch (it needs value ids from the pool and, in a full map, evictions in
+ * batch order), and group / join / modify / compact on LRU maps. */
+#define XE_LRU_PEEK 1u          /* lookup flags: do not promote */
+#define XE_LRU_OLDEST_FIRST 1u  /* order / evict flags: least recently used first (default: most recent first) */
+int xe_lru_lookup_batch_device(xe_vm* vm, int32_t map_idx, const void* d_keys, uint64_t count, void* d_values,
+                               void* d_found, uint32_t flags, void* stream);
+int xe_lru_delete_batch_device(xe_vm* vm, int32_t map_idx, const void* d_keys, uint64_t count, void* d_found,
+                               void* stream);
+int xe_lru_order_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, uint32_t flags, void* d_keys,
+                        void* d_values, uint64_t k, uint64_t* matched, void* stream);
+int xe_lru_evict_device(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, uint32_t flags, void* d_keys,
+                        void* d_values, uint64_t k, uint64_t* matched, void* stream);
+/* The same with host pointers, staged through device buffers of the VM as xe_map_lookup_batch etc. are. */
+int xe_lru_lookup_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t count, void* values, uint8_t* found,
+                        uint32_t flags);
+int xe_lru_delete_batch(xe_vm* vm, int32_t map_idx, const void* keys, uint64_t count, uint8_t* found);
+int xe_lru_order(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, uint32_t flags, void* keys, void* values,
+                 uint64_t k, uint64_t* matched);
+int xe_lru_evict(xe_vm* vm, int32_t map_idx, const xe_map_filter* f, uint32_t flags, void* keys, void* values,
+                 uint64_t k, uint64_t* matched);
+
 /* --- one process, N devices (SURVEY §8b xe_run_batch_multi): the Go host shards a batch over the
  * GPUs of a node through the FFI alone. vms[k] runs on its own device with identical programs, maps
  * and map contents (the caller sets each up the same way). Exchange over RCCL (xGMI) when the devices
