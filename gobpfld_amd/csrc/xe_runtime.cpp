@@ -4291,14 +4291,15 @@ int xe_map_state_import(xe_vm* vm, int32_t mi, const void* d_in, void* stream) {
 namespace {
 constexpr uint64_t kMoMaxCount = 1ull << 31;
 
-// Common start of the batched calls and of scan / expire: pipelined batches complete, the map is of a served
-// kind and current on the device, the per-entry scratch holds `count` slots behind zeroed counters. 1: nothing
-// to do (count 0).
-// Its parts, which the group-by runs for two maps: the map is of a served kind and may be written; ...
-int mapop_map(xe_vm* vm, int32_t mi, bool writes, HostMap** mp) {
+// Common start of every call: pipelined batches complete, the map is of the kind the call serves (ARRAY / HASH,
+// or with `lru` LRU_HASH: the xe_lru_ calls) and current on the device, the per-entry scratch holds `count` slots
+// behind zeroed counters. 1: nothing to do (count 0).
+// Its parts, which group and join run for two maps: the map is of the served kind and may be written; ...
+int mapop_map(xe_vm* vm, int32_t mi, bool writes, HostMap** mp, bool lru = false) {
   HostMap* m = get_map(vm, mi);
   if (!m) return fail(vm, XE_ERR_INVAL, "map index out of bounds");
-  if (m->ordered() || (m->dkind != XE_DM_ARRAY && m->dkind != XE_DM_HASH))
+  if (lru && m->dkind != XE_DM_LRU) return fail(vm, XE_ERR_INVAL, "the xe_lru_ calls serve LRU_HASH maps only");
+  if (!lru && m->dkind != XE_DM_ARRAY && m->dkind != XE_DM_HASH)
     return fail(vm, XE_ERR_UNSUPPORTED, "batched device map operations serve ARRAY and HASH maps only");
   if (m->dkind == XE_DM_ARRAY && m->def.max_entries >= kMoAbsent)
     return fail(vm, XE_ERR_UNSUPPORTED, "batched device map operations: ARRAY map too large");
@@ -4313,7 +4314,9 @@ int mapop_current(xe_vm* vm, HostMap* m) {
   if (map_upload(vm, *m)) return fail(vm, XE_ERR_DEVICE, "map upload");
   return XE_OK;
 }
-// The table of a served map as the kernels read it.
+// The table of a served map as the kernels read it. An LRU map's stamps are current between calls (replicas folded
+// after each launch, the one-lane replay writes them itself, an upload writes ranks); its links are not needed by
+// these calls and are left to lru_relink.
 XeMapView map_view(const HostMap& m) {
   XeMapView v{};
   v.kind = m.dkind;
@@ -4322,11 +4325,18 @@ XeMapView map_view(const HostMap& m) {
   v.max_entries = m.def.max_entries;
   v.cap = m.cap;
   v.kwords = m.kwords;
-  v.rwords = m.dkind == XE_DM_HASH ? xe_hash_rwords(m.kwords) : 0;
+  v.rwords = m.dkind == XE_DM_ARRAY ? 0 : xe_hash_rwords(m.kwords);
   v.recs = m.d_keys;
   v.vals = m.d_vals;
-  v.snap = m.d_snap;
-  v.count = m.d_count;
+  if (m.dkind == XE_DM_LRU) {
+    v.pool_cap = m.pool_cap;
+    v.elen = m.d_elen;
+    v.tag = m.d_tag;
+    v.hdr = m.d_hdr;
+  } else {
+    v.snap = m.d_snap;
+    v.count = m.d_count;
+  }
   return v;
 }
 struct MapOpCall {
@@ -4334,10 +4344,10 @@ struct MapOpCall {
   XeMapOp o{};
   xe_stream_t s = nullptr;
 };
-int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, MapOpCall& c) {
+int mapop_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, MapOpCall& c, bool lru = false) {
   if (!vm) return XE_ERR_INVAL;
   if (int rc = xe_sync(vm)) return rc;
-  if (int rc = mapop_map(vm, mi, writes, &c.m)) return rc;
+  if (int rc = mapop_map(vm, mi, writes, &c.m, lru)) return rc;
   if (count > kMoMaxCount) return fail(vm, XE_ERR_INVAL, "batched map operation: more than 2^31 keys");
   if (set_device(vm->settings.device)) return fail(vm, XE_ERR_DEVICE, "hipSetDevice failed");
   c.s = stream ? (xe_stream_t)stream : vm->stream;
@@ -4356,10 +4366,20 @@ int mapop_steps(xe_vm* vm, const XeMapOp& o, std::initializer_list<uint32_t> ste
     if (xe_launch_mapop(&o, st, (void*)s)) return fail(vm, XE_ERR_DEVICE, "map operation launch");
   return XE_OK;
 }
+// The lookup's launches: FIND, then VALUE for the values too wide to travel with the key's lane.
+int lookup_steps(xe_vm* vm, const XeMapOp& o, xe_stream_t s) {
+  if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
+  return o.value_size > kMoInline ? mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s) : XE_OK;
+}
 // A call wrote map m's device copy: the mirror reads the device again, the staged snapshots no longer match.
 void map_written(xe_vm* vm, HostMap* m) {
   m->dev_dirty = true;
   vm->staged_slot = -1;
+}
+// ... of an LRU map, changing the usage order or removing entries: only the stamps say so until lru_relink runs.
+void lru_written(xe_vm* vm, HostMap* m) {
+  m->links_stale = true;
+  map_written(vm, m);
 }
 // One visit to the host mirror rebuilds the table without its tombstones (map_download: drop_tombstones).
 int compact_via_host(xe_vm* vm, HostMap* m) {
@@ -4421,71 +4441,36 @@ int claim_until_fits(xe_vm* vm, const XeMapOp& o, xe_stream_t s, uint32_t locate
     if (dmemset(o.ctr, 0, (kMoErr + 1) * 4, s)) return fail(vm, XE_ERR_DEVICE, what);
   }
 }
-}  // namespace
-
-extern "C" {
-
-int xe_map_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_values, void* d_found,
-                               void* stream) {
-  MapOpCall c;
-  auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, false, stream, c);
+// What a keyed call was given. The host-pointer forms hand the device forms the staging buffers in these places.
+struct KeyedBufs {
+  const void* keys;
+  const void* values_in;  // (the update's)
+  void* values_out;
+  void* found;
+};
+constexpr auto no_check = [](HostMap*) { return XE_OK; };
+// The opening of the keyed device forms. `missing`: the refusal of a call that has keys to serve but lacks a pointer
+// it requires (null: it has them all); it begins as a call of no keys, so nothing is uploaded for it. `check`: the
+// caller's own refusals, which come before that one. 1: nothing to do; 0: the keys and the outputs are set.
+template <class Check>
+int keyed_begin(xe_vm* vm, int32_t mi, bool lru, bool writes, const KeyedBufs& b, uint64_t count, const char* missing, void* stream,
+                MapOpCall& c, Check check) {
+  const int rc = mapop_begin(vm, mi, missing ? 0 : count, writes, stream, c, lru);
   if (rc < 0) return rc;
-  if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
-  if (rc == 1) return XE_OK;
-  o.keys = (const uint8_t*)d_keys;
-  o.values_out = (uint8_t*)d_values;
-  o.found = (uint8_t*)d_found;
-  if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
-  if (o.value_size > kMoInline)
-    if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s)) return r;
-  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map lookup batch");
+  if (int e = check(c.m)) return e;
+  if (count && missing) return fail(vm, XE_ERR_INVAL, missing);
+  if (rc == 1) return 1;
+  c.o.keys = (const uint8_t*)b.keys;
+  c.o.values_in = (const uint8_t*)b.values_in;
+  c.o.values_out = (uint8_t*)b.values_out;
+  c.o.found = (uint8_t*)b.found;
   return XE_OK;
 }
-
-int xe_map_update_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, const void* d_values, uint64_t count, void* stream) {
-  MapOpCall c;
-  auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, (d_keys && d_values) ? count : 0, true, stream, c);
-  if (rc < 0) return rc;
-  if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
-  if (rc == 1) return XE_OK;
-  o.keys = (const uint8_t*)d_keys;
-  o.values_in = (const uint8_t*)d_values;
-  if (int r = array_win(vm, m, o, s)) return r;
-  uint32_t cnt = 0, fresh = 0;
-  if (int r = claim_until_fits(vm, o, s, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, m, "map update batch", "key out of range", "map is full", &cnt, &fresh))
-    return r;
-  if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY}, s)) return r;
-  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
-  if (m->dkind == XE_DM_HASH) m->live = cnt + fresh;
-  map_written(vm, m);
-  return XE_OK;
-}
-
-int xe_map_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_found, void* stream) {
-  MapOpCall c;
-  auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, d_keys ? count : 0, true, stream, c);
-  if (rc < 0) return rc;
-  if (m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
-  if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
-  if (rc == 1) return XE_OK;
-  o.keys = (const uint8_t*)d_keys;
-  o.found = (uint8_t*)d_found;
-  if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO}, s)) return r;
-  uint32_t cnt = 0;
-  if (d2h(&cnt, m->d_count, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map delete batch");
-  m->live = cnt;
-  map_written(vm, m);
-  return XE_OK;
-}
-
 // Host-pointer forms: stage, run the device form on the VM's stream, copy back. A call the device form refuses
 // or has nothing to do for goes to it unstaged: its checks, its answer.
 //
 // The keys (and the values, if any) to d_mo_keys / d_mo_vals; d_mo_vals / d_mo_found made ready for the call's outputs.
-static int stage_in(xe_vm* vm, const HostMap* m, uint64_t count, const void* keys, const void* values, bool vals_out, bool found_out) {
+int stage_in(xe_vm* vm, const HostMap* m, uint64_t count, const void* keys, const void* values, bool vals_out, bool found_out) {
   const size_t kb = size_t(count) * (m->dkind == XE_DM_ARRAY ? 4 : m->def.key_size), vb = size_t(count) * m->def.value_size;
   set_device(vm->settings.device);
   if (ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb) || ((values || vals_out) && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb)) ||
@@ -4495,45 +4480,29 @@ static int stage_in(xe_vm* vm, const HostMap* m, uint64_t count, const void* key
   return XE_OK;
 }
 // ... and the outputs back (either may be null).
-static int stage_out(xe_vm* vm, const HostMap* m, uint64_t count, void* values, uint8_t* found) {
+int stage_out(xe_vm* vm, const HostMap* m, uint64_t count, void* values, void* found) {
   const size_t vb = size_t(count) * m->def.value_size;
   if ((values && vb && d2h(values, vm->d_mo_vals, vb, vm->stream)) || (found && d2h(found, vm->d_mo_found, size_t(count), vm->stream)) ||
       ((values || found) && dsync(vm->stream)))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
   return XE_OK;
 }
-int xe_map_lookup_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, void* values, uint8_t* found) {
+// `form` is the device form, given the host's pointers (`pass`: the caller's own reasons to go unstaged) or the
+// staging buffers in their places. found_out: the device form reports found[], whether or not the caller wants it.
+template <class Form>
+int staged(xe_vm* vm, int32_t mi, uint64_t count, const KeyedBufs& h, bool pass, bool found_out, Form form) {
   if (!vm) return XE_ERR_INVAL;
   HostMap* m = get_map(vm, mi);
-  if (!m || !count || !keys || !values || count > kMoMaxCount) return xe_map_lookup_batch_device(vm, mi, keys, count, values, found, nullptr);
-  if (int rc = stage_in(vm, m, count, keys, nullptr, true, true)) return rc;
-  if (int rc = xe_map_lookup_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_vals, vm->d_mo_found, nullptr)) return rc;
-  return stage_out(vm, m, count, values, found);
+  if (!m || !count || !h.keys || count > kMoMaxCount || pass) return form(h);
+  if (int rc = stage_in(vm, m, count, h.keys, h.values_in, h.values_out != nullptr, found_out)) return rc;
+  if (int rc = form(KeyedBufs{vm->d_mo_keys, h.values_in ? vm->d_mo_vals : nullptr, h.values_out ? vm->d_mo_vals : nullptr,
+                              found_out ? vm->d_mo_found : nullptr}))
+    return rc;
+  return stage_out(vm, m, count, h.values_out, h.found);
 }
-
-int xe_map_update_batch_staged(xe_vm* vm, int32_t mi, const void* keys, const void* values, uint64_t count) {
-  if (!vm) return XE_ERR_INVAL;
-  HostMap* m = get_map(vm, mi);
-  if (!m || !count || !keys || !values || count > kMoMaxCount) return xe_map_update_batch_device(vm, mi, keys, values, count, nullptr);
-  if (int rc = stage_in(vm, m, count, keys, values, false, false)) return rc;
-  return xe_map_update_batch_device(vm, mi, vm->d_mo_keys, vm->d_mo_vals, count, nullptr);
-}
-
-int xe_map_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, uint8_t* found) {
-  if (!vm) return XE_ERR_INVAL;
-  HostMap* m = get_map(vm, mi);
-  if (!m || !count || !keys || count > kMoMaxCount) return xe_map_delete_batch_device(vm, mi, keys, count, found, nullptr);
-  if (int rc = stage_in(vm, m, count, keys, nullptr, false, true)) return rc;
-  if (int rc = xe_map_delete_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_found, nullptr)) return rc;
-  return stage_out(vm, m, count, nullptr, found);
-}
-
-// Scan and expire (xe_mapops.h SELECT .. EXPIRE). host: keys / values are host memory, staged through
-// d_mo_keys / d_mo_vals once r is known. The per-entry scratch and the staging hold r entries, never
-// cap_entries or the table.
-//
-// The filter checked and set, and the slots a tile pass looks at.
-static int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp& o) {
+// The walk calls (scan, top, stats, group, join, modify, the LRU order). The filter checked and set, and the slots a
+// tile pass looks at.
+int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp& o) {
   const xe_map_filter all{};  // XE_MF_ALL
   if (!f) f = &all;
   if (f->op >= kMfOps) return fail(vm, XE_ERR_INVAL, "map filter: unknown op");
@@ -4550,19 +4519,132 @@ static int map_scan_setup(xe_vm* vm, HostMap* m, const xe_map_filter* f, XeMapOp
   else o.nslots = m->cap;
   return XE_OK;
 }
-// The r entries the bitmap and the tile bases select: SCATTER, COPY, the step `after` on the same entries
-// (XE_MO_SCAN_EXPIRE removes them, XE_MO_MODIFY_EDIT edits them, XE_MO_STEPS: none), the staging back to the
-// host, the synchronisation and the host's view of a map that lost entries or was written. joined (the join's
-// third output, r x o.dst.value_size): JOIN_VALUE behind COPY, in front of `after`.
-static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uint32_t r, void* keys, void* values, uint32_t after,
-                           bool host, const char* what, void* joined = nullptr) {
-  const bool out = keys || values, remove = after == XE_MO_SCAN_EXPIRE, modify = after == XE_MO_MODIFY_EDIT;
-  if (!r || (!remove && !modify && !out && !joined)) return XE_OK;
+// The opening of the walk calls: begin (the counters; the slots come with r), the refusal of a removing call on an
+// ARRAY map, `refuse` (the caller's own refusal, null: none) and of a null `matched`, the filter, the caller's
+// further `checks`, the outputs zeroed, the scratch of the tile passes. 1: the map has no slots to walk.
+// `refuse` is a refusal the caller has already decided on (an unknown flag, a missing output): it is passed as text
+// and not made by the caller because begin's refusals come before it.
+enum : uint32_t {
+  kWalkLru = 1, kWalkWrites = 2, kWalkRemoves = 4,  // the map kind served; the call writes; it removes (and so writes)
+  kWalkBitmap = 8, kWalkEqualBitmap = 16, kWalkBins = 32,  // scan_scratch: the bitmap; the top's second one; its bins
+  kWalkTopScratch = kWalkBitmap | kWalkEqualBitmap | kWalkBins
+};
+template <class Checks>
+int walk_begin(xe_vm* vm, int32_t mi, uint32_t how, const char* refuse, const xe_map_filter* f, uint64_t* matched, uint64_t* second,
+               void* stream, MapOpCall& c, Checks checks) {
+  auto& [m, o, s] = c;
+  if (int rc = mapop_begin(vm, mi, 1, how & (kWalkWrites | kWalkRemoves), stream, c, how & kWalkLru)) return rc;
+  if ((how & kWalkRemoves) && m->dkind == XE_DM_ARRAY) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
+  if (refuse) return fail(vm, XE_ERR_INVAL, refuse);
+  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
+  if (int e = map_scan_setup(vm, m, f, o)) return e;
+  if (int e = checks(m, o)) return e;
+  *matched = 0;
+  if (second) *second = 0;
+  const size_t tiles = xe_ms_tiles(o.nslots);
+  if (!tiles) return 1;
+  if (how & kWalkBitmap)
+    if (int e = scan_scratch(vm, o, tiles, how & kWalkEqualBitmap, how & kWalkBins)) return e;
+  return XE_OK;
+}
+constexpr auto no_checks = [](HostMap*, XeMapOp&) { return XE_OK; };
+// Where a walk call reports its entries: host memory (staged through d_mo_keys / d_mo_vals / d_mo_join once r is
+// known) or device memory. Any of the three may be null. joined: the join's third output, r x o.dst.value_size.
+struct Rows {
+  void *keys, *values, *joined;
+  bool host;
+};
+}  // namespace
+
+extern "C" {
+
+int xe_map_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_values, void* d_found,
+                               void* stream) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const char* missing = d_keys && d_values ? nullptr : "null keys / values";
+  if (int rc = keyed_begin(vm, mi, false, false, {d_keys, nullptr, d_values, d_found}, count, missing, stream, c, no_check)) return rc < 0 ? rc : XE_OK;
+  if (int r = lookup_steps(vm, o, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map lookup batch");
+  return XE_OK;
+}
+
+int xe_map_update_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, const void* d_values, uint64_t count, void* stream) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  const char* missing = d_keys && d_values ? nullptr : "null keys / values";
+  if (int rc = keyed_begin(vm, mi, false, true, {d_keys, d_values, nullptr, nullptr}, count, missing, stream, c, no_check)) return rc < 0 ? rc : XE_OK;
+  if (int r = array_win(vm, m, o, s)) return r;
+  uint32_t cnt = 0, fresh = 0;
+  if (int r = claim_until_fits(vm, o, s, XE_MO_UPDATE_LOCATE, XE_MO_UPDATE_UNDO, m, "map update batch", "key out of range", "map is full", &cnt, &fresh))
+    return r;
+  if (int r = mapop_steps(vm, o, {XE_MO_UPDATE_MARK, XE_MO_UPDATE_COPY}, s)) return r;
+  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map update batch");
+  if (m->dkind == XE_DM_HASH) m->live = cnt + fresh;
+  map_written(vm, m);
+  return XE_OK;
+}
+
+int xe_map_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_found, void* stream) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  auto hash_only = [vm](HostMap* m) { return m->dkind != XE_DM_HASH ? fail(vm, XE_ERR_INVAL, "delete not available on this map type") : XE_OK; };
+  if (int rc = keyed_begin(vm, mi, false, true, {d_keys, nullptr, nullptr, d_found}, count, d_keys ? nullptr : "null keys", stream, c, hash_only))
+    return rc < 0 ? rc : XE_OK;
+  if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND, XE_MO_DELETE_CLAIM, XE_MO_DELETE_ZERO}, s)) return r;
+  uint32_t cnt = 0;
+  if (d2h(&cnt, m->d_count, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map delete batch");
+  m->live = cnt;
+  map_written(vm, m);
+  return XE_OK;
+}
+
+int xe_map_lookup_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, void* values, uint8_t* found) {
+  return staged(vm, mi, count, {keys, nullptr, values, found}, !values, true, [=](const KeyedBufs& b) {
+    return xe_map_lookup_batch_device(vm, mi, b.keys, count, b.values_out, b.found, nullptr);
+  });
+}
+
+int xe_map_update_batch_staged(xe_vm* vm, int32_t mi, const void* keys, const void* values, uint64_t count) {
+  return staged(vm, mi, count, {keys, values, nullptr, nullptr}, !values, false, [=](const KeyedBufs& b) {
+    return xe_map_update_batch_device(vm, mi, b.keys, b.values_in, count, nullptr);
+  });
+}
+
+int xe_map_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, uint8_t* found) {
+  return staged(vm, mi, count, {keys, nullptr, nullptr, found}, false, true, [=](const KeyedBufs& b) {
+    return xe_map_delete_batch_device(vm, mi, b.keys, count, b.found, nullptr);
+  });
+}
+
+// Scan and expire (xe_mapops.h SELECT .. EXPIRE).
+//
+// The r entries the bitmap and the tile bases select: SCATTER, with `ranked` RANK and SORT (the slots in the LRU
+// stamps' order from there on), COPY, JOIN_VALUE, the step `after` on the same entries (XE_MO_SCAN_EXPIRE and
+// XE_MO_LRU_ERASE remove them, XE_MO_MODIFY_EDIT edits them, XE_MO_STEPS: none), the staging back to the host,
+// the synchronisation and the host's view of a map that lost entries or was written. The per-entry scratch and
+// the staging hold r entries, never the caller's cap or the table.
+static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uint32_t r, const Rows& rows, uint32_t after, const char* what,
+                           bool ranked = false) {
+  const auto [keys, values, joined, host] = rows;
+  const bool out = keys || values, expire = after == XE_MO_SCAN_EXPIRE, erase = after == XE_MO_LRU_ERASE;
+  if (!r || (after == XE_MO_STEPS && !out && !joined)) return XE_OK;
   const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size, jb = joined ? size_t(r) * o.dst.value_size : 0;
-  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4)) return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
+  const size_t k8 = (size_t(r) * 8 + 255) & ~size_t(255), s4 = (size_t(r) * 4 + 255) & ~size_t(255);  // the sort's keys, its slots
+  size_t tmp = 0;
+  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4) ||
+      (ranked && (xe_mapop_sort_bytes(r, &tmp) || ensure_buf(&vm->d_relink, &vm->d_relink_cap, 2 * k8 + s4 + tmp))))
+    return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
   o.ctr = (uint32_t*)vm->d_mo;
   o.slot = o.ctr + kMoCounters;
   o.n = r;
+  if (ranked) {
+    o.l_keys = (uint64_t*)vm->d_relink;
+    o.l_keys2 = (uint64_t*)((uint8_t*)vm->d_relink + k8);
+    o.l_slot2 = (uint32_t*)((uint8_t*)vm->d_relink + 2 * k8);
+    o.l_tmp = (uint8_t*)vm->d_relink + 2 * k8 + s4;
+    o.l_tmp_bytes = tmp;
+  }
   if (host && ((keys && ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb)) || (values && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb)) ||
                (joined && ensure_buf(&vm->d_mo_join, &vm->d_mo_join_cap, jb))))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
@@ -4570,44 +4652,41 @@ static int map_scan_report(xe_vm* vm, HostMap* m, XeMapOp& o, xe_stream_t s, uin
   o.values_out = (uint8_t*)(!values ? nullptr : host ? vm->d_mo_vals : values);
   o.j_values = (uint8_t*)(!joined ? nullptr : host ? vm->d_mo_join : joined);
   if (int e = mapop_steps(vm, o, {XE_MO_SCAN_SCATTER}, s)) return e;
+  if (ranked) {
+    if (int e = mapop_steps(vm, o, {XE_MO_LRU_RANK, XE_MO_LRU_SORT}, s)) return e;
+    o.slot = o.l_slot2;  // rank order from here on
+  }
   if (out)
     if (int e = mapop_steps(vm, o, {XE_MO_SCAN_COPY}, s)) return e;
   if (joined && jb)
     if (int e = mapop_steps(vm, o, {XE_MO_JOIN_VALUE}, s)) return e;
   uint32_t cnt = 0;
-  if (remove) {
-    if (int e = mapop_steps(vm, o, {XE_MO_SCAN_EXPIRE}, s)) return e;
-    if (d2h(&cnt, m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, what);
+  if (after != XE_MO_STEPS) {
+    o.l_all = erase;  // (ERASE: every slot it is given, not the claimed ones)
+    if (int e = mapop_steps(vm, o, {after}, s)) return e;
+    if (expire && d2h(&cnt, m->d_count, 4, s)) return fail(vm, XE_ERR_DEVICE, what);
   }
-  if (modify)
-    if (int e = mapop_steps(vm, o, {XE_MO_MODIFY_EDIT}, s)) return e;
   if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s)) ||
                (jb && d2h(joined, vm->d_mo_join, jb, s))))
     return fail(vm, XE_ERR_DEVICE, "map operation staging");
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
-  if (remove) m->live = cnt;
-  if (remove || modify) map_written(vm, m);
+  if (expire) m->live = cnt;
+  if (erase) lru_written(vm, m);
+  else if (after != XE_MO_STEPS) map_written(vm, m);
   return XE_OK;
 }
-static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries,
-                        uint64_t* matched, void* stream, bool expire, bool host) {
+static int map_scan_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const Rows& rows, uint64_t cap_entries, uint64_t* matched, void* stream,
+                        bool expire) {
   MapOpCall c;
   auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, 1, expire, host ? nullptr : stream, c);  // (the counters; slots come with r)
-  if (rc < 0) return rc;
-  if (expire && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
-  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  *matched = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (!tiles) return XE_OK;
-  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  if (int rc = walk_begin(vm, mi, kWalkBitmap | (expire ? kWalkRemoves : 0), nullptr, f, matched, nullptr, stream, c, no_checks))
+    return rc < 0 ? rc : XE_OK;
   if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
   uint32_t total = 0;
   if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map scan");
   *matched = total;
-  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), keys, values,
-                         expire ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, host, expire ? "map expire" : "map scan");
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), rows, expire ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS,
+                         expire ? "map expire" : "map scan");
 }
 
 // Top and evict (xe_mapops.h PREFIX .. TRIM, then the scan's steps): everything up to the final SCAN is
@@ -4622,23 +4701,10 @@ static int map_order_check(xe_vm* vm, HostMap* m, const xe_map_order* ord, XeMap
   o.t_desc = ord->descending;
   return XE_OK;
 }
-static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
-                       uint64_t* matched, uint64_t* cut, void* stream, bool evict, bool host) {
-  MapOpCall c;
-  auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, 1, evict, host ? nullptr : stream, c);
-  if (rc < 0) return rc;
-  if (evict && m->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
-  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  if (int e = map_order_check(vm, m, ord, o)) return e;
-  *matched = 0;
-  if (cut) *cut = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (!tiles) return XE_OK;
-  if (int e = scan_scratch(vm, o, tiles, true, true)) return e;
+// The selection over the field o.t_off / o.t_width / o.t_desc, for the first k; the counters it leaves.
+static int top_select(xe_vm* vm, XeMapOp& o, xe_stream_t s, uint64_t k, const char* what, uint32_t (&ctr)[kMoCounters]) {
   o.t_k = uint32_t(std::min<uint64_t>(k, 0xffffffffu));  // (more than any table holds)
-  if (dmemset(o.bins, 0, kMtBins * 4, s)) return fail(vm, XE_ERR_DEVICE, "map top");
+  if (dmemset(o.bins, 0, kMtBins * 4, s)) return fail(vm, XE_ERR_DEVICE, what);
   for (o.t_pass = 0; o.t_pass < o.t_width; o.t_pass++)
     if (int e = mapop_steps(vm, o, {XE_MO_TOP_PREFIX, XE_MO_TOP_PICK}, s)) return e;
   XeMapOp eq = o;  // the scan's SCAN over the equal counts
@@ -4646,27 +4712,37 @@ static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_m
   if (int e = mapop_steps(vm, o, {XE_MO_TOP_CUT}, s)) return e;
   if (int e = mapop_steps(vm, eq, {XE_MO_SCAN_SCAN}, s)) return e;
   if (int e = mapop_steps(vm, o, {XE_MO_TOP_TRIM, XE_MO_SCAN_SCAN}, s)) return e;
+  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+  return XE_OK;
+}
+static int map_top_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, const Rows& rows, uint64_t k, uint64_t* matched,
+                       uint64_t* cut, void* stream, bool evict) {
+  MapOpCall c;
+  auto& [m, o, s] = c;
+  auto order = [vm, ord](HostMap* m, XeMapOp& o) { return map_order_check(vm, m, ord, o); };
+  if (int rc = walk_begin(vm, mi, kWalkTopScratch | (evict ? kWalkRemoves : 0), nullptr, f, matched, cut, stream, c, order))
+    return rc < 0 ? rc : XE_OK;
   uint32_t ctr[kMoCounters];
-  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map top");
+  if (int e = top_select(vm, o, s, k, "map top", ctr)) return e;
   *matched = ctr[kMtMatched];
   const uint32_t r = ctr[kMoMatched];
   if (cut && r) {
     const uint64_t key = uint64_t(ctr[kMtPrefix]) | uint64_t(ctr[kMtPrefix + 1]) << 32;
     *cut = o.t_desc ? ~key & mt_mask(o.t_width) : key;
   }
-  return map_scan_report(vm, m, o, s, r, keys, values, evict ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, host, evict ? "map evict" : "map top");
+  return map_scan_report(vm, m, o, s, r, rows, evict ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, evict ? "map evict" : "map top");
 }
-static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
+int xe_map_stats(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
   MapOpCall c;
   auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, 1, false, stream, c);
+  auto order = [vm, field](HostMap* m, XeMapOp& o) { return map_order_check(vm, m, field, o); };
+  uint64_t none = 0;  // (the walk's matched: the stats have a count of their own)
+  const char* no_out = out ? nullptr : "null stats";  // (refused after begin's own refusals, as `matched` is elsewhere)
+  const int rc = walk_begin(vm, mi, 0, no_out, f, &none, nullptr, stream, c, order);
   if (rc < 0) return rc;
-  if (!out) return fail(vm, XE_ERR_INVAL, "null stats");
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  if (int e = map_order_check(vm, m, field, o)) return e;
   o.t_desc = 0;
   uint64_t w[4] = {0, 0, 0, 0};  // count, sum, ~min, max
-  if (xe_ms_tiles(o.nslots)) {
+  if (rc == 0) {
     if (int e = mapop_steps(vm, o, {XE_MO_TOP_STATS}, s)) return e;
     if (d2h(w, o.ctr + kMtStats, sizeof w, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map stats");
   }
@@ -4677,20 +4753,38 @@ static int map_stats_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe
   return XE_OK;
 }
 
+// Group and join make a key of map `om` from `len` bytes at `offset` of the source entry's key or value: the bytes
+// lie inside it and are a key of that map. Said in the caller's words: its name, its bytes, the other map.
+struct DerivedWords {
+  const char *call, *bytes, *other;
+};
+static int check_derived_key(xe_vm* vm, const DerivedWords& w, uint32_t from, uint32_t offset, uint32_t len, const HostMap* sm, const HostMap* om) {
+  const std::string call = std::string(w.call) + ": ";
+  const uint32_t src_key = sm->dkind == XE_DM_ARRAY ? 4 : sm->def.key_size;
+  if (uint64_t(offset) + len > (from == XE_MG_KEY ? src_key : sm->def.value_size))
+    return fail(vm, XE_ERR_INVAL, call + "the " + w.bytes + " bytes lie outside the source key / value");
+  if (om->dkind == XE_DM_HASH) {
+    if (!om->def.key_size) return fail(vm, XE_ERR_INVAL, call + "the " + w.other + " has no key bytes");
+    if (len != om->def.key_size) return fail(vm, XE_ERR_INVAL, call + "len must be the " + w.other + "'s key_size");
+  } else if (len != 1 && len != 2 && len != 4) {
+    return fail(vm, XE_ERR_INVAL, call + "len must be 1, 2 or 4 for an ARRAY " + w.other);
+  }
+  return XE_OK;
+}
+// ... and both begin with the two maps: pipelined batches complete, each map of a served kind, `writes` to which.
+static int two_maps(xe_vm* vm, int32_t src, bool src_writes, HostMap** sm, int32_t other, bool other_writes, HostMap** om) {
+  if (!vm) return XE_ERR_INVAL;
+  if (int rc = xe_sync(vm)) return rc;
+  if (int rc = mapop_map(vm, src, src_writes, sm)) return rc;
+  return mapop_map(vm, other, other_writes, om);
+}
+
 // Group (xe_mapops.h SELECT, SCAN on the source, then LOCATE .. ADD): the update's claim_until_fits with the
 // claims made by the source's selected slots. Nothing per entry is allocated.
 static int map_group_check(xe_vm* vm, const HostMap* sm, const HostMap* dm, const xe_map_group_spec* g) {
   if (g->from > XE_MG_VALUE) return fail(vm, XE_ERR_INVAL, "map group: from must be XE_MG_KEY or XE_MG_VALUE");
   if (g->pad) return fail(vm, XE_ERR_INVAL, "map group: pad must be 0");
-  const uint32_t src_key = sm->dkind == XE_DM_ARRAY ? 4 : sm->def.key_size;
-  if (uint64_t(g->offset) + g->len > (g->from == XE_MG_KEY ? src_key : sm->def.value_size))
-    return fail(vm, XE_ERR_INVAL, "map group: the group bytes lie outside the source key / value");
-  if (dm->dkind == XE_DM_HASH) {
-    if (!dm->def.key_size) return fail(vm, XE_ERR_INVAL, "map group: the destination has no key bytes");
-    if (g->len != dm->def.key_size) return fail(vm, XE_ERR_INVAL, "map group: len must be the destination's key_size");
-  } else if (g->len != 1 && g->len != 2 && g->len != 4) {
-    return fail(vm, XE_ERR_INVAL, "map group: len must be 1, 2 or 4 for an ARRAY destination");
-  }
+  if (int e = check_derived_key(vm, {"map group", "group", "destination"}, g->from, g->offset, g->len, sm, dm)) return e;
   if (g->count_off == XE_MG_NONE && g->sum_off == XE_MG_NONE) return fail(vm, XE_ERR_INVAL, "map group: no accumulator");
   if (g->sum_off != XE_MG_NONE && !g->measure_width) return fail(vm, XE_ERR_INVAL, "map group: a sum needs a measure");
   if (g->measure_width) {
@@ -4704,27 +4798,18 @@ static int map_group_check(xe_vm* vm, const HostMap* sm, const HostMap* dm, cons
   if (g->count_off == g->sum_off) return fail(vm, XE_ERR_INVAL, "map group: the accumulators overlap");
   return XE_OK;
 }
-static int map_group_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst, uint64_t* matched,
-                         uint64_t* created, void* stream) {
-  if (!vm) return XE_ERR_INVAL;
-  if (int rc = xe_sync(vm)) return rc;
+int xe_map_group(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst, uint64_t* matched, uint64_t* created,
+                 void* stream) {
   HostMap *sm = nullptr, *dm = nullptr;
-  if (int rc = mapop_map(vm, src, false, &sm)) return rc;
-  if (int rc = mapop_map(vm, dst, true, &dm)) return rc;
+  if (int rc = two_maps(vm, src, false, &sm, dst, true, &dm)) return rc;
   if (!g) return fail(vm, XE_ERR_INVAL, "null map group spec");
   if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
   if (src == dst) return fail(vm, XE_ERR_INVAL, "map group: source and destination are one map");
   if (int rc = map_group_check(vm, sm, dm, g)) return rc;
   MapOpCall c;
   auto& [m, o, s] = c;
-  if (int rc = mapop_begin(vm, src, 1, false, stream, c)) return rc;  // (the counters; no per-entry slots)
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  if (int rc = mapop_current(vm, dm)) return rc;
-  *matched = 0;
-  if (created) *created = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (!tiles) return XE_OK;
-  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  auto current = [vm, dm](HostMap*, XeMapOp&) { return mapop_current(vm, dm); };
+  if (int rc = walk_begin(vm, src, kWalkBitmap, nullptr, f, matched, created, stream, c, current)) return rc < 0 ? rc : XE_OK;
   o.dst = map_view(*dm);
   o.g_from = g->from;
   o.g_off = g->offset;
@@ -4752,11 +4837,6 @@ static int map_group_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const x
   return XE_OK;
 }
 
-int xe_map_group(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_group_spec* g, int32_t dst_map, uint64_t* matched,
-                 uint64_t* created, void* stream) {
-  return map_group_run(vm, src_map, f, g, dst_map, matched, created, stream);
-}
-
 // Join (xe_mapops.h JOIN_SELECT in place of the scan's SELECT, then SCAN and map_scan_report with JOIN_VALUE): the
 // scan's run with a second map that is only read. Only the source is written, and only on removal.
 static int map_join_check(xe_vm* vm, const HostMap* sm, const HostMap* om, const xe_map_join_spec* j) {
@@ -4764,40 +4844,23 @@ static int map_join_check(xe_vm* vm, const HostMap* sm, const HostMap* om, const
   if (j->mode > XE_MJ_ABSENT) return fail(vm, XE_ERR_INVAL, "map join: mode must be XE_MJ_PRESENT or XE_MJ_ABSENT");
   if (j->flags & ~XE_MJ_REMOVE) return fail(vm, XE_ERR_INVAL, "map join: unknown flag");
   if (j->pad) return fail(vm, XE_ERR_INVAL, "map join: pad must be 0");
-  const uint32_t src_key = sm->dkind == XE_DM_ARRAY ? 4 : sm->def.key_size;
-  if (uint64_t(j->offset) + j->len > (j->from == XE_MG_KEY ? src_key : sm->def.value_size))
-    return fail(vm, XE_ERR_INVAL, "map join: the join bytes lie outside the source key / value");
-  if (om->dkind == XE_DM_HASH) {
-    if (!om->def.key_size) return fail(vm, XE_ERR_INVAL, "map join: the other map has no key bytes");
-    if (j->len != om->def.key_size) return fail(vm, XE_ERR_INVAL, "map join: len must be the other map's key_size");
-  } else if (j->len != 1 && j->len != 2 && j->len != 4) {
-    return fail(vm, XE_ERR_INVAL, "map join: len must be 1, 2 or 4 for an ARRAY other map");
-  }
+  if (int e = check_derived_key(vm, {"map join", "join", "other map"}, j->from, j->offset, j->len, sm, om)) return e;
   if ((j->flags & XE_MJ_REMOVE) && sm->dkind != XE_DM_HASH) return fail(vm, XE_ERR_INVAL, "delete not available on this map type");
   return XE_OK;
 }
-static int map_join_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other, void* keys,
-                        void* values, void* joined, uint64_t cap_entries, uint64_t* matched, uint64_t* selected, void* stream,
-                        bool host) {
-  if (!vm) return XE_ERR_INVAL;
-  if (int rc = xe_sync(vm)) return rc;
+static int map_join_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other, const Rows& rows,
+                        uint64_t cap_entries, uint64_t* matched, uint64_t* selected, void* stream) {
   const bool remove = j && (j->flags & XE_MJ_REMOVE);
   HostMap *sm = nullptr, *om = nullptr;
-  if (int rc = mapop_map(vm, src, remove, &sm)) return rc;
-  if (int rc = mapop_map(vm, other, false, &om)) return rc;
+  if (int rc = two_maps(vm, src, remove, &sm, other, false, &om)) return rc;
   if (!j) return fail(vm, XE_ERR_INVAL, "null map join spec");
   if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
   if (int rc = map_join_check(vm, sm, om, j)) return rc;
   MapOpCall c;
   auto& [m, o, s] = c;
-  if (int rc = mapop_begin(vm, src, 1, remove, host ? nullptr : stream, c)) return rc;  // (the counters; slots come with r)
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  if (int rc = mapop_current(vm, om)) return rc;
-  *matched = 0;
-  if (selected) *selected = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (!tiles) return XE_OK;
-  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  auto current = [vm, om](HostMap*, XeMapOp&) { return mapop_current(vm, om); };
+  if (int rc = walk_begin(vm, src, kWalkBitmap | (remove ? kWalkWrites : 0), nullptr, f, matched, selected, stream, c, current))
+    return rc < 0 ? rc : XE_OK;
   o.dst = map_view(*om);
   o.g_from = j->from;
   o.g_off = j->offset;
@@ -4808,17 +4871,17 @@ static int map_join_run(xe_vm* vm, int32_t src, const xe_map_filter* f, const xe
   if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map join");
   *matched = ctr[kMoMatched];
   if (selected) *selected = ctr[kMjSelected];
-  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(ctr[kMoMatched], cap_entries)), keys, values,
-                         remove ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS, host, "map join", joined);
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(ctr[kMoMatched], cap_entries)), rows, remove ? XE_MO_SCAN_EXPIRE : XE_MO_STEPS,
+                         "map join");
 }
 int xe_map_join_device(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other_map, void* d_keys,
                        void* d_values, void* d_other_values, uint64_t cap_entries, uint64_t* matched, uint64_t* selected,
                        void* stream) {
-  return map_join_run(vm, src_map, f, j, other_map, d_keys, d_values, d_other_values, cap_entries, matched, selected, stream, false);
+  return map_join_run(vm, src_map, f, j, other_map, {d_keys, d_values, d_other_values, false}, cap_entries, matched, selected, stream);
 }
 int xe_map_join(xe_vm* vm, int32_t src_map, const xe_map_filter* f, const xe_map_join_spec* j, int32_t other_map, void* keys,
                 void* values, void* other_values, uint64_t cap_entries, uint64_t* matched, uint64_t* selected) {
-  return map_join_run(vm, src_map, f, j, other_map, keys, values, other_values, cap_entries, matched, selected, nullptr, true);
+  return map_join_run(vm, src_map, f, j, other_map, {keys, values, other_values, true}, cap_entries, matched, selected, nullptr);
 }
 
 // Compact (xe_mapops.h MARK, SCAN, REBUILD): the counters are read after SCAN (no tombstone: nothing is
@@ -4864,17 +4927,17 @@ int xe_map_compact(xe_vm* vm, int32_t mi, uint32_t flags, xe_map_compact_info* i
 
 int xe_map_scan_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* d_keys, void* d_values, uint64_t cap_entries,
                        uint64_t* matched, void* stream) {
-  return map_scan_run(vm, mi, f, d_keys, d_values, cap_entries, matched, stream, false, false);
+  return map_scan_run(vm, mi, f, {d_keys, d_values, nullptr, false}, cap_entries, matched, stream, false);
 }
 int xe_map_expire_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* d_keys, void* d_values, uint64_t cap_entries,
                          uint64_t* matched, void* stream) {
-  return map_scan_run(vm, mi, f, d_keys, d_values, cap_entries, matched, stream, true, false);
+  return map_scan_run(vm, mi, f, {d_keys, d_values, nullptr, false}, cap_entries, matched, stream, true);
 }
 int xe_map_scan(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries, uint64_t* matched) {
-  return map_scan_run(vm, mi, f, keys, values, cap_entries, matched, nullptr, false, true);
+  return map_scan_run(vm, mi, f, {keys, values, nullptr, true}, cap_entries, matched, nullptr, false);
 }
 int xe_map_expire(xe_vm* vm, int32_t mi, const xe_map_filter* f, void* keys, void* values, uint64_t cap_entries, uint64_t* matched) {
-  return map_scan_run(vm, mi, f, keys, values, cap_entries, matched, nullptr, true, true);
+  return map_scan_run(vm, mi, f, {keys, values, nullptr, true}, cap_entries, matched, nullptr, true);
 }
 
 // Modify (xe_mapops.h MODIFY_TILE .. MODIFY_KEYED). The edit list checked and copied into the call's descriptor.
@@ -4895,40 +4958,33 @@ static int map_edits_setup(xe_vm* vm, const HostMap* m, const xe_map_edit* edits
 }
 // The walk form. Silent and uncapped (every match is edited, none reported) with a value of up to kMmTileMax
 // bytes: the single pass. Otherwise the scan's SELECT and SCAN, then map_scan_report with the edit behind COPY.
-static int map_modify_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, void* keys,
-                          void* values, uint64_t cap_entries, uint64_t* matched, void* stream, bool host) {
+static int map_modify_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, const Rows& rows,
+                          uint64_t cap_entries, uint64_t* matched, void* stream) {
   MapOpCall c;
   auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, 1, true, host ? nullptr : stream, c);  // (the counters; slots come with r)
-  if (rc < 0) return rc;
-  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  if (int e = map_edits_setup(vm, m, edits, n_edits, o)) return e;
-  *matched = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (!tiles) return XE_OK;
+  auto edit_list = [=](HostMap* m, XeMapOp& o) { return map_edits_setup(vm, m, edits, n_edits, o); };
+  if (int rc = walk_begin(vm, mi, kWalkWrites, nullptr, f, matched, nullptr, stream, c, edit_list)) return rc < 0 ? rc : XE_OK;
   uint32_t total = 0;
-  if (!keys && !values && cap_entries >= m->def.max_entries && o.value_size <= kMmTileMax) {
+  if (!rows.keys && !rows.values && cap_entries >= m->def.max_entries && o.value_size <= kMmTileMax) {
     if (int r = mapop_steps(vm, o, {XE_MO_MODIFY_TILE}, s)) return r;
     if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map modify");
     *matched = total;
     if (total) map_written(vm, m);
     return XE_OK;
   }
-  if (int e = scan_scratch(vm, o, tiles, false, false)) return e;
+  if (int e = scan_scratch(vm, o, xe_ms_tiles(o.nslots), false, false)) return e;
   if (int r = mapop_steps(vm, o, {XE_MO_SCAN_SELECT, XE_MO_SCAN_SCAN}, s)) return r;
   if (d2h(&total, o.ctr + kMoMatched, 4, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, "map modify");
   *matched = total;
-  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), keys, values, XE_MO_MODIFY_EDIT, host,
-                         "map modify");
+  return map_scan_report(vm, m, o, s, uint32_t(std::min<uint64_t>(total, cap_entries)), rows, XE_MO_MODIFY_EDIT, "map modify");
 }
 int xe_map_modify_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, void* d_keys,
                          void* d_values, uint64_t cap_entries, uint64_t* matched, void* stream) {
-  return map_modify_run(vm, mi, f, edits, n_edits, d_keys, d_values, cap_entries, matched, stream, false);
+  return map_modify_run(vm, mi, f, edits, n_edits, {d_keys, d_values, nullptr, false}, cap_entries, matched, stream);
 }
 int xe_map_modify(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_edit* edits, uint32_t n_edits, void* keys, void* values,
                   uint64_t cap_entries, uint64_t* matched) {
-  return map_modify_run(vm, mi, f, edits, n_edits, keys, values, cap_entries, matched, nullptr, true);
+  return map_modify_run(vm, mi, f, edits, n_edits, {keys, values, nullptr, true}, cap_entries, matched, nullptr);
 }
 // The keyed form: the values from before are complete (the lookup's launches) before MARK names one
 // repetition of each present key and KEYED lets it edit.
@@ -4936,22 +4992,12 @@ int xe_map_modify_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64
                                void* d_values, void* d_found, void* stream) {
   MapOpCall c;
   auto& [m, o, s] = c;
-  const int rc = mapop_begin(vm, mi, d_keys ? count : 0, true, stream, c);
+  const int rc = keyed_begin(vm, mi, false, true, {d_keys, nullptr, d_values, d_found}, count, d_keys ? nullptr : "null keys", stream, c, no_check);
   if (rc < 0) return rc;
-  if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
   if (int e = map_edits_setup(vm, m, edits, n_edits, o)) return e;
   if (rc == 1) return XE_OK;
-  o.keys = (const uint8_t*)d_keys;
-  o.values_out = (uint8_t*)d_values;
-  o.found = (uint8_t*)d_found;
   if (int r = array_win(vm, m, o, s)) return r;
-  if (d_values) {
-    if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
-    if (o.value_size > kMoInline)
-      if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s)) return r;
-  } else {
-    if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND}, s)) return r;
-  }
+  if (int r = d_values ? lookup_steps(vm, o, s) : mapop_steps(vm, o, {XE_MO_DELETE_FIND}, s)) return r;
   if (int r = mapop_steps(vm, o, {XE_MO_MODIFY_MARK, XE_MO_MODIFY_KEYED}, s)) return r;
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "map modify batch");
   map_written(vm, m);
@@ -4959,99 +5005,38 @@ int xe_map_modify_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64
 }
 int xe_map_modify_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, const xe_map_edit* edits, uint32_t n_edits, void* values,
                         uint8_t* found) {
-  if (!vm) return XE_ERR_INVAL;
-  HostMap* m = get_map(vm, mi);
-  if (!m || !count || !keys || count > kMoMaxCount) return xe_map_modify_batch_device(vm, mi, keys, count, edits, n_edits, values, found, nullptr);
-  if (int rc = stage_in(vm, m, count, keys, nullptr, values != nullptr, found != nullptr)) return rc;
-  if (int rc = xe_map_modify_batch_device(vm, mi, vm->d_mo_keys, count, edits, n_edits, values ? vm->d_mo_vals : nullptr,
-                                          found ? vm->d_mo_found : nullptr, nullptr))
-    return rc;
-  return stage_out(vm, m, count, values, found);
+  return staged(vm, mi, count, {keys, nullptr, values, found}, false, found != nullptr, [=](const KeyedBufs& b) {
+    return xe_map_modify_batch_device(vm, mi, b.keys, count, edits, n_edits, b.values_out, b.found, nullptr);
+  });
 }
 
 int xe_map_top_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* d_keys, void* d_values, uint64_t k,
                       uint64_t* matched, uint64_t* cut, void* stream) {
-  return map_top_run(vm, mi, f, ord, d_keys, d_values, k, matched, cut, stream, false, false);
+  return map_top_run(vm, mi, f, ord, {d_keys, d_values, nullptr, false}, k, matched, cut, stream, false);
 }
 int xe_map_evict_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* d_keys, void* d_values, uint64_t k,
                         uint64_t* matched, uint64_t* cut, void* stream) {
-  return map_top_run(vm, mi, f, ord, d_keys, d_values, k, matched, cut, stream, true, false);
+  return map_top_run(vm, mi, f, ord, {d_keys, d_values, nullptr, false}, k, matched, cut, stream, true);
 }
 int xe_map_top(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
                uint64_t* matched, uint64_t* cut) {
-  return map_top_run(vm, mi, f, ord, keys, values, k, matched, cut, nullptr, false, true);
+  return map_top_run(vm, mi, f, ord, {keys, values, nullptr, true}, k, matched, cut, nullptr, false);
 }
 int xe_map_evict(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* ord, void* keys, void* values, uint64_t k,
                  uint64_t* matched, uint64_t* cut) {
-  return map_top_run(vm, mi, f, ord, keys, values, k, matched, cut, nullptr, true, true);
-}
-int xe_map_stats(xe_vm* vm, int32_t mi, const xe_map_filter* f, const xe_map_order* field, struct xe_map_stats* out, void* stream) {
-  return map_stats_run(vm, mi, f, field, out, stream);
+  return map_top_run(vm, mi, f, ord, {keys, values, nullptr, true}, k, matched, cut, nullptr, true);
 }
 
-// ---- LRU_HASH maps on the device copy (xe_mapops.h: the lru steps over an LRU view). The stamps are current
-// between calls (replicas folded after each launch, the one-lane replay writes them itself, an upload writes
-// ranks); the links are not needed here and are left to lru_relink.
-static XeMapView lru_view(const HostMap& m) {
-  XeMapView v{};
-  v.kind = XE_DM_LRU;
-  v.key_size = m.def.key_size;
-  v.value_size = m.def.value_size;
-  v.max_entries = m.def.max_entries;
-  v.cap = m.cap;
-  v.kwords = m.kwords;
-  v.rwords = xe_hash_rwords(m.kwords);
-  v.recs = m.d_keys;
-  v.vals = m.d_vals;
-  v.pool_cap = m.pool_cap;
-  v.elen = m.d_elen;
-  v.tag = m.d_tag;
-  v.hdr = m.d_hdr;
-  return v;
-}
-// mapop_begin for an LRU map. 1: nothing to do (count 0).
-static int lru_begin(xe_vm* vm, int32_t mi, uint64_t count, bool writes, void* stream, MapOpCall& c) {
-  if (!vm) return XE_ERR_INVAL;
-  if (int rc = xe_sync(vm)) return rc;
-  c.m = get_map(vm, mi);
-  if (!c.m) return fail(vm, XE_ERR_INVAL, "map index out of bounds");
-  if (c.m->dkind != XE_DM_LRU) return fail(vm, XE_ERR_INVAL, "the xe_lru_ calls serve LRU_HASH maps only");
-  if (writes && vm->epoch_open) return fail(vm, XE_ERR_INVAL, "map writes are refused while a shard epoch is open");
-  if (count > kMoMaxCount) return fail(vm, XE_ERR_INVAL, "batched map operation: more than 2^31 keys");
-  if (set_device(vm->settings.device)) return fail(vm, XE_ERR_DEVICE, "hipSetDevice failed");
-  c.s = stream ? (xe_stream_t)stream : vm->stream;
-  if (!count) return 1;
-  if (int rc = mapop_current(vm, c.m)) return rc;
-  if (ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(count) * 4) || dmemset(vm->d_mo, 0, kMoCounters * 4, c.s))
-    return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
-  static_cast<XeMapView&>(c.o) = lru_view(*c.m);
-  c.o.n = uint32_t(count);
-  c.o.ctr = (uint32_t*)vm->d_mo;
-  c.o.slot = c.o.ctr + kMoCounters;
-  return XE_OK;
-}
-// A call changed the usage order or removed entries: only the stamps say so until lru_relink runs.
-static void lru_written(xe_vm* vm, HostMap* m) {
-  m->links_stale = true;
-  map_written(vm, m);
-}
-
+// ---- LRU_HASH maps on the device copy (xe_mapops.h: the lru steps over an LRU view)
 int xe_lru_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_values, void* d_found,
                                uint32_t flags, void* stream) {
   MapOpCall c;
   auto& [m, o, s] = c;
   const bool promote = !(flags & XE_LRU_PEEK);
-  const int rc = lru_begin(vm, mi, (d_keys && d_values) ? count : 0, promote, stream, c);
-  if (rc < 0) return rc;
-  if (flags & ~XE_LRU_PEEK) return fail(vm, XE_ERR_INVAL, "lru lookup: unknown flag");
-  if (count && (!d_keys || !d_values)) return fail(vm, XE_ERR_INVAL, "null keys / values");
-  if (rc == 1) return XE_OK;
-  o.keys = (const uint8_t*)d_keys;
-  o.values_out = (uint8_t*)d_values;
-  o.found = (uint8_t*)d_found;
-  if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_FIND}, s)) return r;
-  if (o.value_size > kMoInline)
-    if (int r = mapop_steps(vm, o, {XE_MO_LOOKUP_VALUE}, s)) return r;
+  const char* missing = d_keys && d_values ? nullptr : "null keys / values";
+  auto known = [vm, flags](HostMap*) { return (flags & ~XE_LRU_PEEK) ? fail(vm, XE_ERR_INVAL, "lru lookup: unknown flag") : XE_OK; };
+  if (int rc = keyed_begin(vm, mi, true, promote, {d_keys, nullptr, d_values, d_found}, count, missing, stream, c, known)) return rc < 0 ? rc : XE_OK;
+  if (int r = lookup_steps(vm, o, s)) return r;
   if (promote) {  // a fresh run epoch, as a batch run takes one (BatchRun::prepare): above every stamp in the map
     if (vm->lru_epoch >= kLruEpochMax && lru_renumber(vm, s)) return fail(vm, XE_ERR_DEVICE, "LRU renumber");
     o.l_stamp = (++vm->lru_epoch) << 48;
@@ -5065,118 +5050,67 @@ int xe_lru_lookup_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64
 int xe_lru_delete_batch_device(xe_vm* vm, int32_t mi, const void* d_keys, uint64_t count, void* d_found, void* stream) {
   MapOpCall c;
   auto& [m, o, s] = c;
-  const int rc = lru_begin(vm, mi, d_keys ? count : 0, true, stream, c);
-  if (rc < 0) return rc;
-  if (count && !d_keys) return fail(vm, XE_ERR_INVAL, "null keys");
-  if (rc == 1) return XE_OK;
-  o.keys = (const uint8_t*)d_keys;
-  o.found = (uint8_t*)d_found;
+  if (int rc = keyed_begin(vm, mi, true, true, {d_keys, nullptr, nullptr, d_found}, count, d_keys ? nullptr : "null keys", stream, c, no_check))
+    return rc < 0 ? rc : XE_OK;
   if (int r = mapop_steps(vm, o, {XE_MO_DELETE_FIND, XE_MO_LRU_CLAIM, XE_MO_LRU_ERASE}, s)) return r;
   if (dsync(s)) return fail(vm, XE_ERR_DEVICE, "lru delete batch");
   lru_written(vm, m);
   return XE_OK;
 }
 
+// The host-pointer forms also go unstaged to a map of another kind and to a write during a shard epoch.
+static bool lru_unstaged(xe_vm* vm, int32_t mi, bool writes) {
+  const HostMap* m = vm ? get_map(vm, mi) : nullptr;
+  return m && (m->dkind != XE_DM_LRU || (writes && vm->epoch_open));
+}
 int xe_lru_lookup_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, void* values, uint8_t* found, uint32_t flags) {
-  if (!vm) return XE_ERR_INVAL;
-  HostMap* m = get_map(vm, mi);
-  if (!m || m->dkind != XE_DM_LRU || !count || !keys || !values || count > kMoMaxCount || (flags & ~XE_LRU_PEEK) ||
-      (!(flags & XE_LRU_PEEK) && vm->epoch_open))
-    return xe_lru_lookup_batch_device(vm, mi, keys, count, values, found, flags, nullptr);
-  if (int rc = stage_in(vm, m, count, keys, nullptr, true, true)) return rc;
-  if (int rc = xe_lru_lookup_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_vals, vm->d_mo_found, flags, nullptr)) return rc;
-  return stage_out(vm, m, count, values, found);
+  const bool pass = !values || (flags & ~XE_LRU_PEEK) || lru_unstaged(vm, mi, !(flags & XE_LRU_PEEK));
+  return staged(vm, mi, count, {keys, nullptr, values, found}, pass, true, [=](const KeyedBufs& b) {
+    return xe_lru_lookup_batch_device(vm, mi, b.keys, count, b.values_out, b.found, flags, nullptr);
+  });
 }
 
 int xe_lru_delete_batch(xe_vm* vm, int32_t mi, const void* keys, uint64_t count, uint8_t* found) {
-  if (!vm) return XE_ERR_INVAL;
-  HostMap* m = get_map(vm, mi);
-  if (!m || m->dkind != XE_DM_LRU || !count || !keys || count > kMoMaxCount || vm->epoch_open)
-    return xe_lru_delete_batch_device(vm, mi, keys, count, found, nullptr);
-  if (int rc = stage_in(vm, m, count, keys, nullptr, false, true)) return rc;
-  if (int rc = xe_lru_delete_batch_device(vm, mi, vm->d_mo_keys, count, vm->d_mo_found, nullptr)) return rc;
-  return stage_out(vm, m, count, nullptr, found);
+  return staged(vm, mi, count, {keys, nullptr, nullptr, found}, lru_unstaged(vm, mi, true), true, [=](const KeyedBufs& b) {
+    return xe_lru_delete_batch_device(vm, mi, b.keys, count, b.found, nullptr);
+  });
 }
 
-// Order and evict: the top's selection with the stamp as the rank key (everything up to the final SCAN queued
-// without a readback), then SCATTER, RANK and SORT put the r selected slots in rank order for COPY and ERASE.
-static int lru_order_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* keys, void* values, uint64_t k,
-                         uint64_t* matched, void* stream, bool evict, bool host) {
+// Order and evict: the top's selection with the stamp as the rank key, then map_scan_report puts the r selected
+// slots in rank order for COPY and ERASE.
+static int lru_order_run(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, const Rows& rows, uint64_t k, uint64_t* matched,
+                         void* stream, bool evict) {
   MapOpCall c;
   auto& [m, o, s] = c;
-  const int rc = lru_begin(vm, mi, 1, evict, host ? nullptr : stream, c);  // (the counters; slots come with r)
-  if (rc < 0) return rc;
-  if (flags & ~XE_LRU_OLDEST_FIRST) return fail(vm, XE_ERR_INVAL, "lru order: unknown flag");
-  if (!matched) return fail(vm, XE_ERR_INVAL, "null matched");
-  if (int e = map_scan_setup(vm, m, f, o)) return e;
-  if (m->def.key_size) o.nslots = m->cap + 1;  // the table and the nil key's record behind it
-  o.t_off = 0;
-  o.t_width = 8;
-  o.t_desc = (flags & XE_LRU_OLDEST_FIRST) ? 0 : 1;
-  *matched = 0;
-  const size_t tiles = xe_ms_tiles(o.nslots);
-  if (int e = scan_scratch(vm, o, tiles, true, true)) return e;
-  o.t_k = uint32_t(std::min<uint64_t>(k, 0xffffffffu));  // (more than any table holds)
+  const char* unknown = (flags & ~XE_LRU_OLDEST_FIRST) ? "lru order: unknown flag" : nullptr;  // (refused after begin's refusals)
+  auto stamps = [flags](HostMap* m, XeMapOp& o) {
+    if (m->def.key_size) o.nslots = m->cap + 1;  // the table and the nil key's record behind it
+    o.t_off = 0;
+    o.t_width = 8;
+    o.t_desc = (flags & XE_LRU_OLDEST_FIRST) ? 0 : 1;
+    return XE_OK;
+  };
+  if (int rc = walk_begin(vm, mi, kWalkLru | kWalkTopScratch | (evict ? kWalkWrites : 0), unknown, f, matched, nullptr, stream, c, stamps))
+    return rc < 0 ? rc : XE_OK;
   const char* what = evict ? "lru evict" : "lru order";
-  if (dmemset(o.bins, 0, kMtBins * 4, s)) return fail(vm, XE_ERR_DEVICE, what);
-  for (o.t_pass = 0; o.t_pass < o.t_width; o.t_pass++)
-    if (int e = mapop_steps(vm, o, {XE_MO_TOP_PREFIX, XE_MO_TOP_PICK}, s)) return e;
-  XeMapOp eq = o;  // the scan's SCAN over the equal counts
-  eq.tile = o.tile2;
-  if (int e = mapop_steps(vm, o, {XE_MO_TOP_CUT}, s)) return e;
-  if (int e = mapop_steps(vm, eq, {XE_MO_SCAN_SCAN}, s)) return e;
-  if (int e = mapop_steps(vm, o, {XE_MO_TOP_TRIM, XE_MO_SCAN_SCAN}, s)) return e;
   uint32_t ctr[kMoCounters];
-  if (d2h(ctr, o.ctr, sizeof ctr, s) || dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
+  if (int e = top_select(vm, o, s, k, what, ctr)) return e;
   *matched = ctr[kMtMatched];
-  const uint32_t r = ctr[kMoMatched];
-  if (!r || (!evict && !keys && !values)) return XE_OK;
-  // the r entries: slots, the sort's keys and outputs and its own storage, the staging of a host call
-  const size_t kb = size_t(r) * o.key_size, vb = size_t(r) * o.value_size;
-  const size_t k8 = (size_t(r) * 8 + 255) & ~size_t(255), s4 = (size_t(r) * 4 + 255) & ~size_t(255);
-  size_t tmp = 0;
-  if (xe_mapop_sort_bytes(r, &tmp) || ensure_buf(&vm->d_mo, &vm->d_mo_cap, kMoCounters * 4 + size_t(r) * 4) ||
-      ensure_buf(&vm->d_relink, &vm->d_relink_cap, 2 * k8 + s4 + tmp))
-    return fail(vm, XE_ERR_DEVICE, "device alloc (map operation scratch)");
-  if (host && ((keys && ensure_buf(&vm->d_mo_keys, &vm->d_mo_keys_cap, kb)) || (values && ensure_buf(&vm->d_mo_vals, &vm->d_mo_vals_cap, vb))))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
-  o.ctr = (uint32_t*)vm->d_mo;
-  o.slot = o.ctr + kMoCounters;
-  o.n = r;
-  o.l_keys = (uint64_t*)vm->d_relink;
-  o.l_keys2 = (uint64_t*)((uint8_t*)vm->d_relink + k8);
-  o.l_slot2 = (uint32_t*)((uint8_t*)vm->d_relink + 2 * k8);
-  o.l_tmp = (uint8_t*)vm->d_relink + 2 * k8 + s4;
-  o.l_tmp_bytes = tmp;
-  o.keys_out = (uint8_t*)(!keys ? nullptr : host ? vm->d_mo_keys : keys);
-  o.values_out = (uint8_t*)(!values ? nullptr : host ? vm->d_mo_vals : values);
-  if (int e = mapop_steps(vm, o, {XE_MO_SCAN_SCATTER, XE_MO_LRU_RANK, XE_MO_LRU_SORT}, s)) return e;
-  o.slot = o.l_slot2;  // rank order from here on
-  if (keys || values)
-    if (int e = mapop_steps(vm, o, {XE_MO_SCAN_COPY}, s)) return e;
-  if (evict) {
-    o.l_all = 1;
-    if (int e = mapop_steps(vm, o, {XE_MO_LRU_ERASE}, s)) return e;
-  }
-  if (host && ((keys && kb && d2h(keys, vm->d_mo_keys, kb, s)) || (values && vb && d2h(values, vm->d_mo_vals, vb, s))))
-    return fail(vm, XE_ERR_DEVICE, "map operation staging");
-  if (dsync(s)) return fail(vm, XE_ERR_DEVICE, what);
-  if (evict) lru_written(vm, m);
-  return XE_OK;
+  return map_scan_report(vm, m, o, s, ctr[kMoMatched], rows, evict ? XE_MO_LRU_ERASE : XE_MO_STEPS, what, true);
 }
 int xe_lru_order_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* d_keys, void* d_values, uint64_t k,
                         uint64_t* matched, void* stream) {
-  return lru_order_run(vm, mi, f, flags, d_keys, d_values, k, matched, stream, false, false);
+  return lru_order_run(vm, mi, f, flags, {d_keys, d_values, nullptr, false}, k, matched, stream, false);
 }
 int xe_lru_evict_device(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* d_keys, void* d_values, uint64_t k,
                         uint64_t* matched, void* stream) {
-  return lru_order_run(vm, mi, f, flags, d_keys, d_values, k, matched, stream, true, false);
+  return lru_order_run(vm, mi, f, flags, {d_keys, d_values, nullptr, false}, k, matched, stream, true);
 }
 int xe_lru_order(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* keys, void* values, uint64_t k, uint64_t* matched) {
-  return lru_order_run(vm, mi, f, flags, keys, values, k, matched, nullptr, false, true);
+  return lru_order_run(vm, mi, f, flags, {keys, values, nullptr, true}, k, matched, nullptr, false);
 }
 int xe_lru_evict(xe_vm* vm, int32_t mi, const xe_map_filter* f, uint32_t flags, void* keys, void* values, uint64_t k, uint64_t* matched) {
-  return lru_order_run(vm, mi, f, flags, keys, values, k, matched, nullptr, true, true);
+  return lru_order_run(vm, mi, f, flags, {keys, values, nullptr, true}, k, matched, nullptr, true);
 }
 
 int xe_debug_map_traffic(xe_vm* vm, int32_t mi, uint64_t* uploads, uint64_t* downloads) {

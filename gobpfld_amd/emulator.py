@@ -335,37 +335,81 @@ class VM:
     def _is_dev(x) -> bool:
         return hasattr(x, "data_ptr") and bool(getattr(x, "is_cuda", False))
 
-    def _mo_keys(self, m: int, keys):
+    def _key_size(self, m: int) -> int:
         d = self.map_defs[m]
-        ks = 4 if d.type in ARRAY_TYPES else d.key_size  # (list maps: the library refuses them)
+        return 4 if d.type in ARRAY_TYPES else d.key_size  # (list maps: the library refuses them)
+
+    def _synced_device(self, tensor=None):
+        """The device of `tensor` (None: the VM's), once whatever torch has queued on its current stream there is
+        complete: the calls run on the VM's stream."""
+        import torch
+        dev = torch.device("cuda", self.settings.device) if tensor is None else tensor.device
+        torch.cuda.current_stream(dev).synchronize()
+        return dev
+
+    def _mo_keys(self, m: int, keys):
+        ks = self._key_size(m)
         if self._is_dev(keys):
             import torch
             k = keys.contiguous().view(torch.uint8).reshape(-1)
-            # the calls run on the VM's stream: whatever torch has queued to produce the tensors completes first
-            torch.cuda.current_stream(k.device).synchronize()
+            self._synced_device(k)
         else:
             k = np.ascontiguousarray(keys).view(np.uint8).reshape(-1)
         n = len(k) // ks if ks else len(keys)
         assert n * ks == len(k), "keys: a whole number of key_size-byte keys"
         return k, n
 
+    @staticmethod
+    def _c_filter(flt):
+        """(the xe_map_filter of `flt`, which has to outlive the call; what to pass for it)."""
+        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        return cf, None if cf is None else C.byref(cf)
+
+    @staticmethod
+    def _out(shape, dev):
+        """(an output array of `shape`, what to pass for it): a CUDA tensor on `dev`, or with dev None zeros on the
+        host. The calls write every entry they report, so the tensor needs no fill kernel on torch's stream, which the
+        VM's stream could overtake. An output of no rows is passed as NULL on either side (the keyed host forms used
+        to pass the empty array's address): a call of no keys or no room returns before it looks at the pointer."""
+        if dev is None:
+            a = np.zeros(shape, dtype=np.uint8)
+            return a, a.ctypes.data if shape[0] else None
+        import torch
+        a = torch.empty(shape, dtype=torch.uint8, device=dev)
+        return a, a.data_ptr() or None
+
+    def _keyed(self, m: int, keys, name: str, what: str, values: bool = True, pre=(), post=()):
+        """A keyed call `name` (with _device for CUDA keys): the outputs (values[n, value_size] if `values`, found[n]).
+        pre / post: the call's own arguments in front of and behind the outputs."""
+        k, n = self._mo_keys(m, keys)
+        dev = k.device if self._is_dev(k) else None
+        outs = [self._out((n, self.map_defs[m].value_size), dev)] if values else []
+        outs.append(self._out((n,), dev))
+        ptrs = [p for _, p in outs]
+        if dev is None:
+            rc = getattr(self.lib, name)(self.h, m, k.ctypes.data, n, *pre, *ptrs, *post)
+        else:
+            rc = getattr(self.lib, name + "_device")(self.h, m, k.data_ptr() or None, n, *pre, *ptrs, *post, None)
+        self._check(rc, what)
+        return tuple(a for a, _ in outs)
+
+    def _rows(self, what: str, n, widths, cap, on_device: bool, call, count=None, rows: int | None = None):
+        """A walk call that reports rows: [output[r, width] for width in widths] + [matched], r = min(matched, cap).
+        call(*pointers, cap) and count() (run first when cap is None: then every match is fetched) make the library
+        call and return its code; n is the c_uint64 they have matched written to. rows: room for this many rows
+        instead of cap."""
+        dev = self._synced_device() if on_device else None
+        if cap is None:  # count first, then fetch all
+            self._check(count(), what)
+            cap = n.value
+        outs = [self._out((cap if rows is None else rows, w), dev) for w in widths]
+        self._check(call(*[p for _, p in outs], cap), what)
+        r = min(int(n.value), cap)  # (the call writes the r entries it reports; the rest is cut off)
+        return [a[:r] for a, _ in outs] + [int(n.value)]
+
     def map_lookup_batch(self, m: int, keys):
         """(values[n, value_size], found[n]) of n keys, read from the device copy of the map."""
-        d = self.map_defs[m]
-        k, n = self._mo_keys(m, keys)
-        if self._is_dev(k):
-            import torch
-            # (the call writes every byte: no fill kernels on torch's stream that its own stream could overtake)
-            vals = torch.empty((n, d.value_size), dtype=torch.uint8, device=k.device)
-            found = torch.empty(n, dtype=torch.uint8, device=k.device)
-            rc = self.lib.map_lookup_batch_device(self.h, m, k.data_ptr() or None, n, vals.data_ptr() or None,
-                                                  found.data_ptr() or None, None)
-        else:
-            vals = np.zeros((n, d.value_size), dtype=np.uint8)
-            found = np.zeros(n, dtype=np.uint8)
-            rc = self.lib.map_lookup_batch(self.h, m, k.ctypes.data, n, vals.ctypes.data, found.ctypes.data)
-        self._check(rc, "map lookup batch")
-        return vals, found
+        return self._keyed(m, keys, "map_lookup_batch", "map lookup batch")
 
     def map_update_batch_device(self, m: int, keys, values) -> None:
         """All-or-nothing update of n keys on the device copy (xe_map_update_batch_device): the result of
@@ -377,7 +421,7 @@ class VM:
             assert self._is_dev(values), "keys and values: both on the device, or both on the host"
             v = values.contiguous().view(torch.uint8).reshape(-1)
             assert len(v) == n * d.value_size
-            torch.cuda.current_stream(v.device).synchronize()
+            self._synced_device(v)
             rc = self.lib.map_update_batch_device(self.h, m, k.data_ptr() or None, v.data_ptr() or None, n, None)
         else:
             v = np.ascontiguousarray(values).view(np.uint8).reshape(-1)
@@ -387,47 +431,18 @@ class VM:
 
     def map_delete_batch(self, m: int, keys):
         """Delete n keys on the device copy; found[n] = the key was present before the call."""
-        k, n = self._mo_keys(m, keys)
-        if self._is_dev(k):
-            import torch
-            found = torch.empty(n, dtype=torch.uint8, device=k.device)
-            rc = self.lib.map_delete_batch_device(self.h, m, k.data_ptr() or None, n, found.data_ptr() or None, None)
-        else:
-            found = np.zeros(n, dtype=np.uint8)
-            rc = self.lib.map_delete_batch(self.h, m, k.ctypes.data, n, found.ctypes.data)
-        self._check(rc, "map delete batch")
-        return found
+        return self._keyed(m, keys, "map_delete_batch", "map delete batch", values=False)[0]
 
     # ---- scan and expire on the device copy (ARRAY / HASH; xe_map_scan_device / xe_map_expire_device)
     def _map_scan(self, m: int, flt, cap, on_device: bool, expire: bool):
-        d = self.map_defs[m]
-        ks = 4 if d.type in ARRAY_TYPES else d.key_size
-        what = "map expire" if expire else "map scan"
-        dev_fn = self.lib.map_expire_device if expire else self.lib.map_scan_device
-        host_fn = self.lib.map_expire if expire else self.lib.map_scan
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
-        fp = None if cf is None else C.byref(cf)
+        what, name = ("map expire", "map_expire") if expire else ("map scan", "map_scan")
+        fn = getattr(self.lib, name + ("_device" if on_device else ""))
+        cf, fp = self._c_filter(flt)
         n = C.c_uint64(0)
-        if on_device:
-            import torch
-            dev = torch.device("cuda", self.settings.device)
-            # the calls run on the VM's stream: whatever torch has queued on its own completes first
-            torch.cuda.current_stream(dev).synchronize()
-        if cap is None:  # count first, then fetch all
-            self._check(self.lib.map_scan_device(self.h, m, fp, None, None, 0, C.byref(n), None), what)
-            cap = n.value
-        if on_device:
-            # (the call writes the r entries it reports; the rest is cut off below)
-            keys = torch.empty((cap, ks), dtype=torch.uint8, device=dev)
-            vals = torch.empty((cap, d.value_size), dtype=torch.uint8, device=dev)
-            rc = dev_fn(self.h, m, fp, keys.data_ptr() or None, vals.data_ptr() or None, cap, C.byref(n), None)
-        else:
-            keys = np.zeros((cap, ks), dtype=np.uint8)
-            vals = np.zeros((cap, d.value_size), dtype=np.uint8)
-            rc = host_fn(self.h, m, fp, keys.ctypes.data if cap else None, vals.ctypes.data if cap else None, cap, C.byref(n))
-        self._check(rc, what)
-        r = min(int(n.value), cap)
-        return keys[:r], vals[:r], int(n.value)
+        stream = (None,) if on_device else ()
+        return tuple(self._rows(what, n, (self._key_size(m), self.map_defs[m].value_size), cap, on_device,
+                                lambda kp, vp, cap: fn(self.h, m, fp, kp, vp, cap, C.byref(n), *stream),
+                                lambda: self.lib.map_scan_device(self.h, m, fp, None, None, 0, C.byref(n), None)))
 
     def map_scan(self, m: int, flt: "MapFilter | None" = None, cap: int | None = None, on_device: bool = False):
         """(keys[r, key_size], values[r, value_size], matched): the entries of the device copy that satisfy
@@ -454,99 +469,54 @@ class VM:
         applied in place to the first r = min(matched, cap) entries of the device copy that satisfy `flt`, in
         map_scan's order; the values are those from before the edits. cap None: every match (counted first, then
         fetched). report False: nothing is reported and only matched is returned. on_device: CUDA tensors."""
-        d = self.map_defs[m]
-        ks = 4 if d.type in ARRAY_TYPES else d.key_size
         ce, ne = self._c_edits(edits)
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
-        fp = None if cf is None else C.byref(cf)
+        cf, fp = self._c_filter(flt)
         n = C.c_uint64(0)
-        if on_device:
-            import torch
-            dev = torch.device("cuda", self.settings.device)
-            # the calls run on the VM's stream: whatever torch has queued on its own completes first
-            torch.cuda.current_stream(dev).synchronize()
         if not report:
+            if on_device:
+                self._synced_device()
             room = (1 << 64) - 1 if cap is None else cap
             self._check(self.lib.map_modify_device(self.h, m, fp, ce, ne, None, None, room, C.byref(n), None), "map modify")
             return int(n.value)
-        if cap is None:  # count first, then fetch all
-            self._check(self.lib.map_scan_device(self.h, m, fp, None, None, 0, C.byref(n), None), "map modify")
-            cap = n.value
-        if on_device:
-            # (the call writes the r entries it reports; the rest is cut off below)
-            keys = torch.empty((cap, ks), dtype=torch.uint8, device=dev)
-            vals = torch.empty((cap, d.value_size), dtype=torch.uint8, device=dev)
-            rc = self.lib.map_modify_device(self.h, m, fp, ce, ne, keys.data_ptr() or None, vals.data_ptr() or None, cap,
-                                            C.byref(n), None)
-        else:
-            keys = np.zeros((cap, ks), dtype=np.uint8)
-            vals = np.zeros((cap, d.value_size), dtype=np.uint8)
-            rc = self.lib.map_modify(self.h, m, fp, ce, ne, keys.ctypes.data if cap else None, vals.ctypes.data if cap else None,
-                                     cap, C.byref(n))
-        self._check(rc, "map modify")
-        r = min(int(n.value), cap)
-        return keys[:r], vals[:r], int(n.value)
+        fn, stream = (self.lib.map_modify_device, (None,)) if on_device else (self.lib.map_modify, ())
+        return tuple(self._rows("map modify", n, (self._key_size(m), self.map_defs[m].value_size), cap, on_device,
+                                lambda kp, vp, cap: fn(self.h, m, fp, ce, ne, kp, vp, cap, C.byref(n), *stream),
+                                lambda: self.lib.map_scan_device(self.h, m, fp, None, None, 0, C.byref(n), None)))
 
     def map_modify_batch(self, m: int, keys, edits, on_device: bool | None = None):
         """(values_before[n, value_size], found[n]): the `edits` applied in place to the entries of n keys on
         the device copy, once per distinct present key; absent keys are reported and nothing is created.
         on_device None: CUDA tensors for keys give tensors back (xe_map_modify_batch_device), numpy arrays go
         through staging; True / False: the keys are moved to the device / the host first."""
-        d = self.map_defs[m]
         if on_device is not None and on_device != self._is_dev(keys):
             if on_device:
                 import torch
                 keys = torch.from_numpy(np.ascontiguousarray(keys).view(np.uint8)).to(torch.device("cuda", self.settings.device))
             else:
                 keys = keys.cpu().numpy()
-        k, n = self._mo_keys(m, keys)
-        ce, ne = self._c_edits(edits)
-        if self._is_dev(k):
-            import torch
-            vals = torch.empty((n, d.value_size), dtype=torch.uint8, device=k.device)
-            found = torch.empty(n, dtype=torch.uint8, device=k.device)
-            rc = self.lib.map_modify_batch_device(self.h, m, k.data_ptr() or None, n, ce, ne, vals.data_ptr() or None,
-                                                  found.data_ptr() or None, None)
-        else:
-            vals = np.zeros((n, d.value_size), dtype=np.uint8)
-            found = np.zeros(n, dtype=np.uint8)
-            rc = self.lib.map_modify_batch(self.h, m, k.ctypes.data, n, ce, ne, vals.ctypes.data, found.ctypes.data)
-        self._check(rc, "map modify batch")
-        return vals, found
+        return self._keyed(m, keys, "map_modify_batch", "map modify batch", pre=self._c_edits(edits))
 
     # ---- top-K, evict and statistics on the device copy (xe_map_top_device / xe_map_evict_device / xe_map_stats)
     def _map_top(self, m: int, order: "MapOrder", k: int, flt, on_device: bool, ranked: bool, evict: bool):
         d = self.map_defs[m]
-        ks = 4 if d.type in ARRAY_TYPES else d.key_size
-        what = "map evict" if evict else "map top"
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
-        fp = None if cf is None else C.byref(cf)
+        what, name = ("map evict", "map_evict") if evict else ("map top", "map_top")
+        fn = getattr(self.lib, name + ("_device" if on_device else ""))
+        cf, fp = self._c_filter(flt)
         co = N.MapOrder(order.offset, order.width, int(order.descending), 0)
         n, cut = C.c_uint64(0), C.c_uint64(0)
-        room = min(k, d.max_entries)  # (r <= matched <= max_entries: no buffer of k entries for a huge k)
-        if on_device:
-            import torch
-            dev = torch.device("cuda", self.settings.device)
-            torch.cuda.current_stream(dev).synchronize()  # the calls run on the VM's stream
-            keys = torch.empty((room, ks), dtype=torch.uint8, device=dev)
-            vals = torch.empty((room, d.value_size), dtype=torch.uint8, device=dev)
-            fn = self.lib.map_evict_device if evict else self.lib.map_top_device
-            rc = fn(self.h, m, fp, C.byref(co), keys.data_ptr() or None, vals.data_ptr() or None, k, C.byref(n), C.byref(cut), None)
-        else:
-            keys = np.zeros((room, ks), dtype=np.uint8)
-            vals = np.zeros((room, d.value_size), dtype=np.uint8)
-            fn = self.lib.map_evict if evict else self.lib.map_top
-            rc = fn(self.h, m, fp, C.byref(co), keys.ctypes.data if room else None, vals.ctypes.data if room else None, k,
-                    C.byref(n), C.byref(cut))
-        self._check(rc, what)
-        r = min(int(n.value), k)
-        keys, vals = keys[:r], vals[:r]
+        stream = (None,) if on_device else ()
+        # (r <= matched <= max_entries: no buffer of k entries for a huge k)
+        keys, vals, matched = self._rows(what, n, (self._key_size(m), d.value_size), k, on_device,
+                                         lambda kp, vp, k: fn(self.h, m, fp, C.byref(co), kp, vp, k, C.byref(n), C.byref(cut), *stream),
+                                         rows=min(k, d.max_entries))
+        r = len(keys)
         if ranked and r > 1:  # the call reports in slot order: a stable sort on the field keeps the tie order
             if on_device:
-                f = torch.zeros(r, dtype=torch.int64, device=dev)
+                import torch
+                f = torch.zeros(r, dtype=torch.int64, device=keys.device)
                 for b in range(order.width):
                     f |= vals[:, order.offset + b].to(torch.int64) << (8 * b)
-                f ^= torch.tensor(-(1 << 63), dtype=torch.int64, device=dev)  # unsigned order through signed compares
+                f ^= torch.tensor(-(1 << 63), dtype=torch.int64, device=keys.device)  # unsigned order through signed compares
                 if order.descending:
                     f = ~f
                 idx = torch.sort(f, stable=True).indices
@@ -556,7 +526,7 @@ class VM:
                     f |= vals[:, order.offset + b].astype(np.uint64) << np.uint64(8 * b)
                 idx = np.argsort(~f if order.descending else f, kind="stable")
             keys, vals = keys[idx], vals[idx]
-        return keys, vals, int(n.value), int(cut.value)
+        return keys, vals, matched, int(cut.value)
 
     def map_top(self, m: int, order: "MapOrder", k: int, flt: "MapFilter | None" = None, on_device: bool = False,
                 ranked: bool = True):
@@ -572,21 +542,20 @@ class VM:
 
     def map_stats(self, m: int, field: "MapOrder", flt: "MapFilter | None" = None) -> dict:
         """{count, sum (mod 2^64), min, max} of `field` over the entries `flt` selects (xe_map_stats)."""
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        cf, fp = self._c_filter(flt)
         co = N.MapOrder(field.offset, field.width, 0, 0)
         out = N.MapStats()
-        self._check(self.lib.map_stats(self.h, m, None if cf is None else C.byref(cf), C.byref(co), C.byref(out), None), "map stats")
+        self._check(self.lib.map_stats(self.h, m, fp, C.byref(co), C.byref(out), None), "map stats")
         return {"count": out.count, "sum": out.sum, "min": out.min, "max": out.max}
 
     def map_group(self, src: int, dst: int, group: "MapGroup", flt: "MapFilter | None" = None) -> tuple[int, int]:
         """(matched, created): the entries of map `src` that `flt` selects, folded by `group` into the
         accumulators of map `dst`'s entries on the device (xe_map_group); created: the new HASH entries."""
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
+        cf, fp = self._c_filter(flt)
         cg = N.MapGroup(group.from_, group.offset, group.len, group.measure_off, group.measure_width, group.count_off,
                         group.sum_off, 0)
         n, new = C.c_uint64(0), C.c_uint64(0)
-        self._check(self.lib.map_group(self.h, src, None if cf is None else C.byref(cf), C.byref(cg), dst, C.byref(n),
-                                       C.byref(new), None), "map group")
+        self._check(self.lib.map_group(self.h, src, fp, C.byref(cg), dst, C.byref(n), C.byref(new), None), "map group")
         return int(n.value), int(new.value)
 
     def map_join(self, src: int, other: int, join: "MapJoin", flt: "MapFilter | None" = None, cap: int | None = None,
@@ -596,41 +565,21 @@ class VM:
         (matched of them), in map_scan's order; r = min(matched, cap). cap None: count first, then fetch them
         all. other_values: also the values of the entries of `other` they joined with (zeros under MJ_ABSENT).
         remove: the r returned entries are removed from `src` (HASH). on_device: CUDA tensors (xe_map_join_device)."""
-        d, od = self.map_defs[src], self.map_defs[other]
-        ks = 4 if d.type in ARRAY_TYPES else d.key_size
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
-        fp = None if cf is None else C.byref(cf)
+        cf, fp = self._c_filter(flt)
         cj0 = N.MapJoin(join.from_, join.offset, join.len, join.mode, 0, 0)  # (counting removes nothing)
         cj = N.MapJoin(join.from_, join.offset, join.len, join.mode, MJ_REMOVE if remove else 0, 0)
         n, sel = C.c_uint64(0), C.c_uint64(0)
-        if on_device:
-            import torch
-            dev = torch.device("cuda", self.settings.device)
-            # the calls run on the VM's stream: whatever torch has queued on its own completes first
-            torch.cuda.current_stream(dev).synchronize()
-        if cap is None:  # count first, then fetch all
-            self._check(self.lib.map_join_device(self.h, src, fp, C.byref(cj0), other, None, None, None, 0, C.byref(n),
-                                                 C.byref(sel), None), "map join")
-            cap = n.value
-        if on_device:
-            # (the call writes the r entries it reports; the rest is cut off below)
-            keys = torch.empty((cap, ks), dtype=torch.uint8, device=dev)
-            vals = torch.empty((cap, d.value_size), dtype=torch.uint8, device=dev)
-            ovals = torch.empty((cap, od.value_size), dtype=torch.uint8, device=dev) if other_values else None
-            rc = self.lib.map_join_device(self.h, src, fp, C.byref(cj), other, keys.data_ptr() or None, vals.data_ptr() or None,
-                                          (ovals.data_ptr() or None) if other_values else None, cap, C.byref(n), C.byref(sel), None)
-        else:
-            keys = np.zeros((cap, ks), dtype=np.uint8)
-            vals = np.zeros((cap, d.value_size), dtype=np.uint8)
-            ovals = np.zeros((cap, od.value_size), dtype=np.uint8) if other_values else None
-            rc = self.lib.map_join(self.h, src, fp, C.byref(cj), other, keys.ctypes.data if cap else None,
-                                   vals.ctypes.data if cap else None, ovals.ctypes.data if other_values and cap else None, cap,
-                                   C.byref(n), C.byref(sel))
-        self._check(rc, "map join")
-        r = min(int(n.value), cap)
-        if other_values:
-            return keys[:r], vals[:r], ovals[:r], int(n.value), int(sel.value)
-        return keys[:r], vals[:r], int(n.value), int(sel.value)
+        fn, stream = (self.lib.map_join_device, (None,)) if on_device else (self.lib.map_join, ())
+        widths = [self._key_size(src), self.map_defs[src].value_size] + ([self.map_defs[other].value_size] if other_values else [])
+
+        def call(kp, vp, *rest):
+            return fn(self.h, src, fp, C.byref(cj), other, kp, vp, rest[0] if other_values else None, rest[-1], C.byref(n), C.byref(sel),
+                      *stream)
+
+        def count():
+            return self.lib.map_join_device(self.h, src, fp, C.byref(cj0), other, None, None, None, 0, C.byref(n), C.byref(sel), None)
+
+        return tuple(self._rows("map join", n, widths, cap, on_device, call, count) + [int(sel.value)])
 
     def map_compact(self, m: int, count_only: bool = False) -> dict:
         """{tombstones, moved, longest_run, via_host}: every tombstone of HASH map `m` removed on the device
@@ -644,59 +593,23 @@ class VM:
     def lru_lookup_batch(self, m: int, keys, peek: bool = False):
         """(values[n, value_size], found[n]) of n keys of LRU_HASH map `m`, read from the device copy. Without
         `peek` the found keys are promoted as map_lookup key by key in order promotes them."""
-        d = self.map_defs[m]
-        k, n = self._mo_keys(m, keys)
-        flags = LRU_PEEK if peek else 0
-        if self._is_dev(k):
-            import torch
-            vals = torch.empty((n, d.value_size), dtype=torch.uint8, device=k.device)
-            found = torch.empty(n, dtype=torch.uint8, device=k.device)
-            rc = self.lib.lru_lookup_batch_device(self.h, m, k.data_ptr() or None, n, vals.data_ptr() or None,
-                                                  found.data_ptr() or None, flags, None)
-        else:
-            vals = np.zeros((n, d.value_size), dtype=np.uint8)
-            found = np.zeros(n, dtype=np.uint8)
-            rc = self.lib.lru_lookup_batch(self.h, m, k.ctypes.data, n, vals.ctypes.data, found.ctypes.data, flags)
-        self._check(rc, "lru lookup batch")
-        return vals, found
+        return self._keyed(m, keys, "lru_lookup_batch", "lru lookup batch", post=(LRU_PEEK if peek else 0,))
 
     def lru_delete_batch(self, m: int, keys):
         """Delete n keys of LRU_HASH map `m` on the device copy; found[n] = the key was present before the call."""
-        k, n = self._mo_keys(m, keys)
-        if self._is_dev(k):
-            import torch
-            found = torch.empty(n, dtype=torch.uint8, device=k.device)
-            rc = self.lib.lru_delete_batch_device(self.h, m, k.data_ptr() or None, n, found.data_ptr() or None, None)
-        else:
-            found = np.zeros(n, dtype=np.uint8)
-            rc = self.lib.lru_delete_batch(self.h, m, k.ctypes.data, n, found.ctypes.data)
-        self._check(rc, "lru delete batch")
-        return found
+        return self._keyed(m, keys, "lru_delete_batch", "lru delete batch", values=False)[0]
 
     def _lru_order(self, m: int, k: int, flt, oldest_first: bool, on_device: bool, evict: bool):
         d = self.map_defs[m]
-        what = "lru evict" if evict else "lru order"
-        dev_fn = self.lib.lru_evict_device if evict else self.lib.lru_order_device
-        host_fn = self.lib.lru_evict if evict else self.lib.lru_order
-        cf = None if flt is None else N.MapFilter(flt.op, flt.offset, flt.width, 0, flt.operand)
-        fp = None if cf is None else C.byref(cf)
+        what, name = ("lru evict", "lru_evict") if evict else ("lru order", "lru_order")
+        fn = getattr(self.lib, name + ("_device" if on_device else ""))
+        cf, fp = self._c_filter(flt)
         flags = LRU_OLDEST_FIRST if oldest_first else 0
         k = min(int(k), d.max_entries)  # (no more entries than the map holds come back)
         n = C.c_uint64(0)
-        if on_device:
-            import torch
-            dev = torch.device("cuda", self.settings.device)
-            torch.cuda.current_stream(dev).synchronize()
-            keys = torch.empty((k, d.key_size), dtype=torch.uint8, device=dev)
-            vals = torch.empty((k, d.value_size), dtype=torch.uint8, device=dev)
-            rc = dev_fn(self.h, m, fp, flags, keys.data_ptr() or None, vals.data_ptr() or None, k, C.byref(n), None)
-        else:
-            keys = np.zeros((k, d.key_size), dtype=np.uint8)
-            vals = np.zeros((k, d.value_size), dtype=np.uint8)
-            rc = host_fn(self.h, m, fp, flags, keys.ctypes.data if k else None, vals.ctypes.data if k else None, k, C.byref(n))
-        self._check(rc, what)
-        r = min(int(n.value), k)
-        return keys[:r], vals[:r], int(n.value)
+        stream = (None,) if on_device else ()
+        return tuple(self._rows(what, n, (d.key_size, d.value_size), k, on_device,
+                                lambda kp, vp, k: fn(self.h, m, fp, flags, kp, vp, k, C.byref(n), *stream)))
 
     def lru_order(self, m: int, k: int, flt: "MapFilter | None" = None, oldest_first: bool = False, on_device: bool = False):
         """(keys[r, key_size], values[r, value_size], matched): the r = min(k, matched) entries of LRU_HASH map
