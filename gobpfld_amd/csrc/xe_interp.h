@@ -1260,7 +1260,8 @@ XE_DEV void hdr_write(XeLane& L, int off, int size, uint64_t x) {
 
 // packet ByteMemory access through the header window when possible. A per-program kernel's
 // XE_HDR_LO is the least offset its packet-read analysis proved for any read (XE_HDR_LO_PROVEN), so a
-// load needs no lower-bound test there; stores are not part of the analysis and keep it.
+// load needs no lower-bound test there; stores are not part of the analysis and keep it. A store goes
+// to HBM and to every byte of it the window holds, so the window never serves a byte from before it.
 XE_DEV bool in_window(const XeLane& L, int64_t off, int size) {
 #if XE_HDR_LO > 0
   if (off < XE_HDR_LO) return false;
@@ -1281,7 +1282,15 @@ XE_DEV uint64_t pkt_load(const XeLane& L, int64_t off, int size) {
 }
 XE_DEV void pkt_store(XeLane& L, int64_t off, int size, uint64_t x) {
   store_le(L.pkt + off, size, x);
-  if (in_window(L, off, size)) hdr_write(L, int(off), size, x);
+  if (in_window(L, off, size)) { hdr_write(L, int(off), size, x); return; }
+  // a store across an edge of the window: write through the bytes inside it, so a later load served
+  // from the window sees them (the caller checked 0 <= off, off + size <= plen)
+  if (off >= L.hdr_len || off + size <= XE_HDR_LO) return;
+#pragma unroll 1
+  for (int b = 0; b < size; b++) {
+    const int o = int(off) + b;
+    if (o >= XE_HDR_LO && o < L.hdr_len) *hdr_at(L, o + L.hsh) = uint8_t(x >> (8 * b));
+  }
 }
 
 // Atomic little-endian add of `add` into the `size`-byte field at p (any alignment), truncating

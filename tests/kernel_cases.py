@@ -78,6 +78,9 @@ def gpu_cases():
         prog, maps, entries, settings = gen_ordered_program(seed)
         settings.engine = JIT
         cases.append((prog, maps, entries, settings))
+    # the header-window programs (tests/window_cases.py): one kernel per read range and store pattern
+    import window_cases as WC
+    cases += WC.kernel_cases()
     return cases
 
 
